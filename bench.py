@@ -11,12 +11,19 @@ stream under backward + fused SGD-momentum/WD update, on 256 synthetic
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
         --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 5
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
-`roofline` for the dominant grad-sync kernel (the fused SGD update:
-20 B/param algorithmic, timed with HIP events on the stream it runs on),
-`grad_sync` (RCCL bus bandwidth of the bucket all-reduces, events on the
-libgsync comm stream, against (n-1) x 153 GB/s xGMI) and `cpu_baseline`
-(the reference's torch-DDP/gloo path on the host cores, rank 0 at N=1).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps`
+steps, writes `--dump-outputs DIR` if asked and prints the line: the contract
+fields (`ms_per_step` = the timed region / `--steps`) and the `roofline` of the
+fused update's launches inside the timed steps (20 B/param algorithmic, HIP
+events on the stream it runs on).  With `--full` the legs after the timed
+region run as well and the line carries them: `roofline` beyond the Infinity
+Cache, `grad_sync` (the tail split; RCCL bus bandwidth of the bucket
+all-reduces, events on the libgsync comm stream, against (n-1) x 153 GB/s
+xGMI), `grad_sync_kernels`, `parity`, `zero2`, `colossal`, `torch_ddp`
+(vs_baseline), `bucket_policy_ab` and `cpu_baseline` (the reference's
+torch-DDP/gloo path on the host cores, rank 0 at N=1).
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 from __future__ import annotations
 
@@ -28,6 +35,15 @@ import sys
 import time
 
 T_START = time.time()  # --wall-budget-s counts from here (covers warm-up's MIOpen compiles)
+
+# With an empty user find-db MIOpen's Find times every applicable solver of every
+# convolution in the first step, its naive reference kernels included: 55 s of the 66 s
+# first step of ResNet-50 x 256.  Reference kernels do not win a Find against the tuned
+# solvers, so Find leaves them out here: first step 11 s, the timed steps unchanged
+# (43.3 against 43.4 ms a step, cold runs on one MI355X).  Set before torch loads MIOpen;
+# a value the caller set stays.
+for _d in ("FWD", "BWD", "WRW"):
+    os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_" + _d, "0")
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
@@ -136,7 +152,66 @@ def parse():
                          "same model / batch / step, timed like the headline; vs_baseline = libgsync / it; "
                          "and configs[4] on torch beside the colossal leg (0: off)")
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "pmc_traffic.json"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything beside the headline: the tail split, the "
+                         "parity step, the standalone collectives, the kernel rates, the zero2 / colossal / torch "
+                         "legs, the bucket-policy A/B and the CPU baseline, each as its own option sets it; "
+                         "without --full none of them runs, whatever their options say")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: put the model and the optimizer state back to what they were "
+                         "before the first step, run the timed path once more on the same batch (untimed) and "
+                         "write what it returns and leaves as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+# --dump-outputs: the updated parameters are sampled above this many elements (fp32: 32 MB of the 64 MB a dump may take)
+DUMP_SAMPLE_ELEMS = 8 * 1024 * 1024
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step holds after it, as float32 .npy files in
+    `out_dir`:
+
+    * ``loss.npy``: the loss the step returned (one element);
+    * ``params.npy``: the updated parameters, each flattened (logical order) and
+      concatenated in ``model.parameters()`` order; above DUMP_SAMPLE_ELEMS
+      elements a fixed sample of them (indices drawn once with numpy's
+      default_rng(DUMP_SAMPLE_SEED), sorted: the same for every run of the same
+      model);
+    * ``buffers.npy``: the module buffers (BatchNorm running statistics and batch
+      counts) concatenated.
+
+    The step that is dumped is one more run of the timed path after the timed steps,
+    from the state before the first step (main() restores the parameters and buffers
+    and clears the optimizer state) on the same batch: model seed, input seed, weights
+    and batch are then the same in every run with the same arguments, and so is the
+    result up to the rounding of one step (two cold runs of ResNet-50 x 256: loss and
+    buffers bit for bit, the parameters within 3e-3 to 4e-3 of their scale; torch's
+    deterministic convolution mode would remove that too, but MIOpen finds no algorithm
+    for these bf16 channels_last convolutions under it).  The state the timed steps themselves end
+    in is not comparable between two runs: MIOpen's backward is not bitwise
+    repeatable, and W + N steps of SGD at lr 0.1 on a randomly initialised ResNet
+    amplify that rounding (two runs of one build, 2 + 5 steps: parameters apart by up
+    to 0.5, running variances by 1.9)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        flats = [p.detach().reshape(-1) for p in model.parameters()]
+        flat = torch.cat([f.float() for f in flats]) if flats else torch.zeros(0)
+        if flat.numel() > DUMP_SAMPLE_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, flat.numel(), DUMP_SAMPLE_ELEMS))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        bufs = [b.detach().reshape(-1).float() for b in model.buffers()]
+        np.save(os.path.join(out_dir, "params.npy"), flat.cpu().numpy())
+        np.save(os.path.join(out_dir, "buffers.npy"), (torch.cat(bufs) if bufs else torch.zeros(0)).cpu().numpy())
+        if torch.is_tensor(loss):
+            np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
 
 
 def collective_bench(ddp, zero, world, iters=10, warmup=3):
@@ -1320,6 +1395,13 @@ def main():
             raise SystemExit("--graph: DDP engine only")
         run = D.CapturedStep(train_step, optimizers=[opt], warmup=max(1, args.warmup - 1))
 
+    dump_snap = None
+    if args.dump_outputs:
+        if zero is not None or torch_zero:
+            # their fp32 master shards live in the engine, not in the model: nothing here puts them back
+            raise SystemExit("--dump-outputs: the ddp and colossal engines only")
+        dump_snap = ([p.detach().clone() for p in model.parameters()], [b.detach().clone() for b in model.buffers()])
+
     t_w0 = time.time()
     for i in range(args.warmup):
         t_i = time.time()
@@ -1356,9 +1438,27 @@ def main():
             from distributed_training_amd import _lib as L
 
             zero_ms_saved = zero.plan.timer_read(kind=L.GS_OP_SGD if args.optimizer == "sgd" else L.GS_OP_ADAM)
+    if dump_snap is not None:
+        # --dump-outputs (see dump_outputs): every rank puts back the state of before the first step, in place
+        # (the addresses a recorded graph and the buckets hold stay valid), and runs the timed path once more
+        with torch.no_grad():
+            for t, s0 in zip(list(model.parameters()) + list(model.buffers()), dump_snap[0] + dump_snap[1]):
+                t.copy_(s0)
+            opts = opt._opts() + [opt.main] if isinstance(opt, _OverlappedStep) else [opt]
+            for o in opts:  # momentum / moment buffers and tensor step counts: as a first step finds them
+                for st in o.state.values():
+                    for v in st.values():
+                        if torch.is_tensor(v):
+                            v.zero_()
+        dump_loss = step()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, dump_loss)
+        del dump_snap, dump_loss
+        if args.impl == "libgsync" and not args.graph:
+            opt.kernel_ms()  # drop the untimed step's launch
     # the headline's own numbers, complete before any leg below
-    if args.impl == "torch":
-        opt_ms = []
+    if args.impl == "torch" or (args.graph and not args.full):
+        opt_ms = []  # graph mode's update-kernel figure takes launches of its own: with --full
     elif zero is None and args.graph:
         # replays carry no timing events: time the update kernel over a few eager
         # launches on the same state after the timed region (same kernel, same plan)
@@ -1590,6 +1690,10 @@ def main():
     # recorded there too instead of losing the line; a leg still running when the
     # budget ends (a hung collective) gets a watchdog that prints the line with the
     # legs completed so far and ends every rank with exit status 3.
+    # All of them need --full: a plain run tears down and prints the line from here.
+    if not args.full:
+        args.parity = args.kernel_rates = args.zero_leg = args.colossal_leg = args.torch_leg = 0
+        args.collective_bench = args.policy_ab = args.cpu_baseline = 0
     tail = timeline = tail_timed = None
     coll = kernel_rates = parity = policy_ab = zero2 = colossal = torch_ddp = None
     leg_errors: dict = {}
@@ -1636,7 +1740,7 @@ def main():
             leg_seconds[name] = round(time.perf_counter() - t_leg, 2)
 
     watchdog = None
-    if budget > 0:
+    if budget > 0 and args.full:
         import threading
 
         def expire():
@@ -1681,7 +1785,8 @@ def main():
             ddp.set_timeline(1)
             opt.kernel_ms()  # drop the untimed steps' launches
 
-    leg("tail_split", tail_leg)
+    if args.full:
+        leg("tail_split", tail_leg)
 
     if args.parity and args.impl == "libgsync" and not args.graph:
         from distributed_training_amd import parity as PC

@@ -7,6 +7,6 @@ OUT=gpurun_out; mkdir -p $OUT
 for r in 1 2; do
   for tu in ${TUS:-512 0}; do
     echo "== tu=$tu round $r" >> $OUT/ab_update.log
-    GSYNC_UPDATE_TASK_UNITS=$tu timeout -k 10 400 python -u bench.py --cpu-baseline 0 ${BENCH_ARGS:-} >> $OUT/ab_update.log 2>> $OUT/ab_update.err || exit 1
+    GSYNC_UPDATE_TASK_UNITS=$tu timeout -k 10 400 python -u bench.py --full --cpu-baseline 0 ${BENCH_ARGS:-} >> $OUT/ab_update.log 2>> $OUT/ab_update.err || exit 1
   done
 done

@@ -8,7 +8,7 @@ while IFS= read -r args; do
   [ -z "$args" ] && continue
   i=$((i+1))
   echo "== variant $i: $args" | tee -a $OUT/variants.log
-  timeout -k 10 ${VT:-400} python -u bench.py --gpus 1 $args >> $OUT/variants.log 2>> $OUT/variants.err
+  timeout -k 10 ${VT:-400} python -u bench.py --full --gpus 1 $args >> $OUT/variants.log 2>> $OUT/variants.err
   rc=$?
   echo "rc=$rc" | tee -a $OUT/variants.log
   tail -1 $OUT/variants.log

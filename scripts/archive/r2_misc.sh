@@ -9,7 +9,7 @@ TAG=${TAG:-r2h}
 export TMPDIR=/tmp
 TAG=$TAG bash scripts/gpu_tests.sh || exit $?
 echo "== roctx marker trace"
-GSYNC_ROCTX=1 timeout -k 10 600 rocprofv3 --marker-trace --kernel-trace --stats -f csv -d $OUT/mk_$TAG -o bench -- python3 -u bench.py --steps 3 --warmup 2 --cpu-baseline 0 --parity 0 > $OUT/${TAG}_marker_bench.json 2> $OUT/${TAG}_marker.err || { tail -20 $OUT/${TAG}_marker.err; exit 1; }
+GSYNC_ROCTX=1 timeout -k 10 600 rocprofv3 --marker-trace --kernel-trace --stats -f csv -d $OUT/mk_$TAG -o bench -- python3 -u bench.py --full --steps 3 --warmup 2 --cpu-baseline 0 --parity 0 > $OUT/${TAG}_marker_bench.json 2> $OUT/${TAG}_marker.err || { tail -20 $OUT/${TAG}_marker.err; exit 1; }
 for f in $(find $OUT/mk_$TAG -name "*stats*.csv"); do cp $f $OUT/${TAG}_marker_$(basename $f); done
 python3 - $OUT/mk_$TAG $OUT/${TAG}_marker_ranges.json <<'PY'
 import csv, glob, json, os, sys, collections
@@ -30,5 +30,5 @@ print(json.dumps({k: v[0] for k, v in agg.items()}))
 PY
 rm -rf $OUT/mk_$TAG
 echo "== MIOpen Find experiment (cudnn.benchmark=1)"
-timeout -k 10 700 python -u bench.py --steps 20 --warmup 5 --cudnn-benchmark 1 --cpu-baseline 0 --parity 0 > $OUT/${TAG}_bench_find.json 2> $OUT/${TAG}_bench_find.err
+timeout -k 10 700 python -u bench.py --full --steps 20 --warmup 5 --cudnn-benchmark 1 --cpu-baseline 0 --parity 0 > $OUT/${TAG}_bench_find.json 2> $OUT/${TAG}_bench_find.err
 echo "find rc=$?"; cat $OUT/${TAG}_bench_find.json | cut -c1-300; grep "warmup step" $OUT/${TAG}_bench_find.err

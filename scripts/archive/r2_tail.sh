@@ -13,7 +13,7 @@ for tp in 1 0; do
 for cap in none 1; do
   echo "== bench tail_on_producer=$tp last-bucket cap $cap"
   extra=""; [ $cap != none ] && extra="--last-bucket-cap-mb $cap"
-  GSYNC_TAIL_ON_PRODUCER=$tp timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 --cpu-baseline 0 --kernel-rates 0 $extra > $OUT/${TAG}_bench_tp${tp}_cap_$cap.json 2> $OUT/${TAG}_bench_tp${tp}_cap_$cap.err || { tail -20 $OUT/${TAG}_bench_tp${tp}_cap_$cap.err; exit 1; }
+  GSYNC_TAIL_ON_PRODUCER=$tp timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --kernel-rates 0 $extra > $OUT/${TAG}_bench_tp${tp}_cap_$cap.json 2> $OUT/${TAG}_bench_tp${tp}_cap_$cap.err || { tail -20 $OUT/${TAG}_bench_tp${tp}_cap_$cap.err; exit 1; }
   python3 -c "
 import json
 d=[json.loads(l) for l in open('$OUT/${TAG}_bench_tp${tp}_cap_$cap.json') if l.startswith('{')][0]

@@ -11,11 +11,11 @@ timeout -k 10 600 python -u -m pytest -m gpu -x -q --timeout 300 --timeout-metho
 rc=$?; tail -3 $OUT/pytest.log; [ $rc -ne 0 ] && exit $rc
 for r in 1 2; do
   for ext in 1 0; do
-    GS_TIMER_EXT=$ext timeout -k 10 400 python -u bench.py --gpus 1 --cpu-baseline 0 --parity 0 > $OUT/bench_ext${ext}_r$r.json 2> $OUT/bench_ext${ext}_r$r.err || { tail $OUT/bench_ext${ext}_r$r.err; exit 1; }
+    GS_TIMER_EXT=$ext timeout -k 10 400 python -u bench.py --full --gpus 1 --cpu-baseline 0 --parity 0 > $OUT/bench_ext${ext}_r$r.json 2> $OUT/bench_ext${ext}_r$r.err || { tail $OUT/bench_ext${ext}_r$r.err; exit 1; }
   done
 done
 export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof -o bench -- python3 -u bench.py --gpus 1 --steps 20 --warmup 3 --cpu-baseline 0 --parity 0 --kernel-rates 0 > $OUT/prof_bench.json 2> $OUT/prof.err || { tail -20 $OUT/prof.err; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof -o bench -- python3 -u bench.py --full --gpus 1 --steps 20 --warmup 3 --cpu-baseline 0 --parity 0 --kernel-rates 0 > $OUT/prof_bench.json 2> $OUT/prof.err || { tail -20 $OUT/prof.err; exit 1; }
 python3 scripts/trace_roofline.py $(find $OUT/prof -name "*kernel_trace.csv" | head -1) 20 $OUT/trace_roofline_r4i.json || true
 for f in $(find $OUT/prof -name "*stats*.csv"); do cp $f $OUT/r4i_$(basename $f); done
 rm -rf $OUT/prof

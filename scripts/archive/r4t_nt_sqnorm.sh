@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/r4t; mkdir -p $OUT
-timeout -k 10 400 python -u bench.py --gpus 1 > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --gpus 1 > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 timeout -k 10 200 python -u scripts/sqnorm_chain.py > $OUT/chain_default.jsonl 2> $OUT/chain.err || { tail $OUT/chain.err; exit 1; }
 timeout -k 10 600 python -u -m pytest tests/test_clip_fold.py tests/test_zero_ds_step.py tests/test_gpu_zero.py tests/test_gpu_kernels.py -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/pytest.log 2>&1; rc=$?; tail -3 $OUT/pytest.log
 python3 - <<'PY'

@@ -95,5 +95,5 @@ def wrap(name, before=False):
 wrap("grad_sync_kernel_rates", before=True)
 for name in ("zero2_leg", "colossal_leg", "torch_ddp_leg", "torch_colossal_leg"):
     wrap(name)
-sys.argv = ["bench.py", "--cpu-baseline", "0"]
+sys.argv = ["bench.py", "--cpu-baseline", "0", "--full"]
 bench.main()

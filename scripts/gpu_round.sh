@@ -30,14 +30,14 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
   echo "== bench"
-  timeout -k 10 900 python -u bench.py --gpus 1 --steps $STEPS --warmup $WARM ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -20 $OUT/bench_$TAG.err; exit 1; }
+  timeout -k 10 900 python -u bench.py --full --gpus 1 --steps $STEPS --warmup $WARM ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -20 $OUT/bench_$TAG.err; exit 1; }
   cat $OUT/bench_$TAG.json
 fi
 export TMPDIR=/tmp
 if [ "${PROFILE:-0}" == "1" ]; then
   echo "== rocprofv3 kernel trace + stats (bench)"
   # the timed steps only after the warmup: no kernel-rate / parity launches in the trace
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_$TAG -o bench -- python3 -u bench.py --gpus 1 --steps $STEPS --warmup 3 --cpu-baseline 0 --kernel-rates 0 --parity 0 ${BENCH_ARGS:-} > $OUT/prof_bench_$TAG.json 2> $OUT/prof_$TAG.err || { tail -20 $OUT/prof_$TAG.err; exit 1; }
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_$TAG -o bench -- python3 -u bench.py --full --gpus 1 --steps $STEPS --warmup 3 --cpu-baseline 0 --kernel-rates 0 --parity 0 ${BENCH_ARGS:-} > $OUT/prof_bench_$TAG.json 2> $OUT/prof_$TAG.err || { tail -20 $OUT/prof_$TAG.err; exit 1; }
   find $OUT/prof_$TAG -name "*stats*"
   python3 scripts/overlap.py $(find $OUT/prof_$TAG -name "*kernel_trace.csv" | head -1) $OUT/overlap_$TAG.json > /dev/null || true
   python3 scripts/trace_roofline.py $(find $OUT/prof_$TAG -name "*kernel_trace.csv" | head -1) $STEPS $OUT/trace_roofline_$TAG.json || true

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/r2matrix; mkdir -p $OUT
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 400 python -u bench.py --steps 20 --warmup 4 --cpu-baseline 0 --kernel-rates 0 "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "FAIL $name"; tail -5 $OUT/$name.err; return 1; }
+  timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 4 --cpu-baseline 0 --kernel-rates 0 "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "FAIL $name"; tail -5 $OUT/$name.err; return 1; }
   grep '^{' $OUT/$name.json | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); p=d.get('parity') or {}; r=d.get('roofline') or {}
 print(json.dumps({'name': '$name', 'args': '$*', 'value': round(d['value'],1), 'ms_per_step': round(d['ms_per_step'],3), 'dtype': d['dtype'], 'parity_ok': p.get('ok'), 'update_frac': None if not r else round(r['frac'],3), 'tail_us': round(((d.get('grad_sync') or {}).get('tail_ms') or {}).get('total_timed_step', 0)*1e3,1)}))" | tee -a $OUT/summary.jsonl

@@ -7,7 +7,7 @@ i=0
 while IFS= read -r v; do
   i=$((i+1))
   echo "== $i: $v"
-  timeout -k 10 400 python -u bench.py --cpu-baseline 0 --kernel-rates 0 $v > $OUT/v$i.json 2> $OUT/v$i.err || { tail -5 $OUT/v$i.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --cpu-baseline 0 --kernel-rates 0 $v > $OUT/v$i.json 2> $OUT/v$i.err || { tail -5 $OUT/v$i.err; exit 1; }
   grep '^{' $OUT/v$i.json | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); g=d['grad_sync']; t=g.get('tail_ms') or {}
 print(json.dumps({'args': '''$v''', 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'opt_ms': d['roofline']['avg_launch_ms'],

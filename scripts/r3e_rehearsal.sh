@@ -10,7 +10,7 @@ OUT=gpurun_out; mkdir -p $OUT
 export OUT
 P=$((29500 + RANDOM % 1000))
 GSYNC_BENCH_TRACEBACK_S=60 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-  --master-addr 127.0.0.1 --master-port $P bench.py --gpus 4 --pg-backend gloo --steps 5 --warmup 2 \
+  --master-addr 127.0.0.1 --master-port $P bench.py --full --gpus 4 --pg-backend gloo --steps 5 --warmup 2 \
   --cpu-baseline 0 --kernel-rates 0 > $OUT/r3e_n4_gloo_r50.json 2> $OUT/r3e_n4_gloo_r50.err
 rc=$?; echo "rehearsal rc=$rc"; tail -3 $OUT/r3e_n4_gloo_r50.err; [ $rc -ne 0 ] && exit $rc
 python3 -c "import json; d=json.loads(open('$OUT/r3e_n4_gloo_r50.json').read().strip().splitlines()[-1]); print('value', d['value'], 'parity', d['parity']['ok'], 'ab', d.get('bucket_policy_ab', {}).get('decision'))"

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out; mkdir -p $OUT
 P=$((29500 + RANDOM % 1000))
 GSYNC_BENCH_TRACEBACK_S=120 timeout -k 10 1000 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-  --master-addr 127.0.0.1 --master-port $P bench.py --gpus 4 --pg-backend gloo --steps 5 --warmup 2 \
+  --master-addr 127.0.0.1 --master-port $P bench.py --full --gpus 4 --pg-backend gloo --steps 5 --warmup 2 \
   > $OUT/r3t_n4_gloo_legs.json 2> $OUT/r3t_n4_gloo_legs.err
 rc=$?; echo "rc=$rc"; grep "\[bench\]" $OUT/r3t_n4_gloo_legs.err | tail -12
 python3 -c "

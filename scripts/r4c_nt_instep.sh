@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/r4c; mkdir -p $OUT
 for r in 1 2; do
   for v in ${VARIANTS:-base ntg ntst ntupd ntall}; do
-    GSYNC_LIB=distributed_training_amd/lib/variants/libgsync_$v.so timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 3 --cpu-baseline 0 --parity 0 > $OUT/bench_${v}_r$r.json 2> $OUT/bench_${v}_r$r.err || { tail $OUT/bench_${v}_r$r.err; exit 1; }
+    GSYNC_LIB=distributed_training_amd/lib/variants/libgsync_$v.so timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 3 --cpu-baseline 0 --parity 0 > $OUT/bench_${v}_r$r.json 2> $OUT/bench_${v}_r$r.err || { tail $OUT/bench_${v}_r$r.err; exit 1; }
     echo "$v r$r done"
   done
 done

@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/r4d; mkdir -p $OUT
 BUDGET=${BUDGET:-240}
 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-  --master-port 29561 bench.py --gpus 4 --pg-backend gloo --steps 5 --warmup 2 --wall-budget-s $BUDGET \
+  --master-port 29561 bench.py --full --gpus 4 --pg-backend gloo --steps 5 --warmup 2 --wall-budget-s $BUDGET \
   > $OUT/n4_budget$BUDGET.json 2> $OUT/n4_budget$BUDGET.err
 rc=$?; echo "rc=$rc"
 tail -c 1500 $OUT/n4_budget$BUDGET.json

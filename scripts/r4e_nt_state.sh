@@ -7,12 +7,12 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/r4e; mkdir -p $OUT
-timeout -k 10 400 python -u bench.py --gpus 1 --cpu-baseline 0 > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail $OUT/bench_default.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --gpus 1 --cpu-baseline 0 > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail $OUT/bench_default.err; exit 1; }
 for r in 1 2; do
   for cfg in "adam:--optimizer adam" "r152:--model resnet152 --batch 128"; do
     n=${cfg%%:*}; a=${cfg#*:}
     for pol in 0 2; do
-      GS_NT_STATE=$pol timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 3 --cpu-baseline 0 --parity 0 --kernel-rates 0 $a > $OUT/bench_${n}_nts${pol}_r$r.json 2> $OUT/bench_${n}_nts${pol}_r$r.err || { tail $OUT/bench_${n}_nts${pol}_r$r.err; exit 1; }
+      GS_NT_STATE=$pol timeout -k 10 400 python -u bench.py --full --gpus 1 --steps 20 --warmup 3 --cpu-baseline 0 --parity 0 --kernel-rates 0 $a > $OUT/bench_${n}_nts${pol}_r$r.json 2> $OUT/bench_${n}_nts${pol}_r$r.err || { tail $OUT/bench_${n}_nts${pol}_r$r.err; exit 1; }
       echo "$n nts=$pol r$r done"
     done
   done

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/r5a; mkdir -p $OUT
 timeout -k 10 90 scripts/micro/event_chain > $OUT/event_chain.jsonl 2> $OUT/event_chain.err || { cat $OUT/event_chain.err; exit 1; }
 cat $OUT/event_chain.jsonl
-timeout -k 10 700 python -u bench.py --gpus 1 --steps 20 --warmup 5 --zero-leg 1 --colossal-leg 1 > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 700 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --zero-leg 1 --colossal-leg 1 > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$OUT/bench.json'))
 print(d['value'], d.get('leg_seconds'), d.get('leg_errors'), d.get('warmup_s'))

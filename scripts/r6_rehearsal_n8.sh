@@ -13,7 +13,7 @@ TAG=${TAG:-r6n8}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp GSYNC_BENCH_TRACEBACK_S=60
 timeout -k 10 ${LIMIT:-1100} python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-  --master-port ${PORT:-29611} bench.py --gpus 8 --steps 20 --warmup 5 --pg-backend gloo --batch ${BATCH:-64} \
+  --master-port ${PORT:-29611} bench.py --full --gpus 8 --steps 20 --warmup 5 --pg-backend gloo --batch ${BATCH:-64} \
   --wall-budget-s ${BUDGET:-900} ${BENCH_ARGS:-} > $OUT/n8_gloo.json 2> $OUT/n8_gloo.err
 rc=$?
 grep -v "^Thread\|^  File\|^Current thread\|^Timeout" $OUT/n8_gloo.err | grep "\[bench\]" | tail -30

@@ -16,7 +16,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
   echo "smoke ok"
 fi
-timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
 python3 - "$OUT/bench.json" <<'PY'
 import json, sys
 d = [json.loads(l) for l in open(sys.argv[1]) if l.startswith("{")][-1]
@@ -35,7 +35,7 @@ b = k.get("beyond_ic", {}).get("kernels", {})
 print("beyond_ic", {n: (round(v["frac"], 3), round(v.get("frac_of_live_ceiling") or 0, 3)) for n, v in b.items()})
 PY
 if [ "${PROFILE:-1}" == "1" ]; then
-  timeout -k 10 700 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof -o bench -- python3 -u bench.py --cpu-baseline 0 > $OUT/prof_bench.json 2> $OUT/prof_bench.err || { tail -20 $OUT/prof_bench.err; exit 1; }
+  timeout -k 10 700 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof -o bench -- python3 -u bench.py --full --cpu-baseline 0 > $OUT/prof_bench.json 2> $OUT/prof_bench.err || { tail -20 $OUT/prof_bench.err; exit 1; }
   python3 scripts/trace_bench.py $(find $OUT/prof -name "*kernel_trace.csv" | head -1) 5 20 20 "$TAG" $OUT/trace_roofline.json
   for f in $(find $OUT/prof -name "*stats*.csv"); do cp $f $OUT/${TAG}_$(basename $f); done
   rm -rf $OUT/prof

@@ -20,6 +20,7 @@ def test_compiles(path):
 def test_bench_defaults_parse():
     code = ("import sys; sys.argv=['bench.py']; sys.path.insert(0, %r); import bench; a = bench.parse(); "
             "assert a.gpus == 1 and a.steps == 20 and a.warmup == 5 and a.engine == 'ddp' and a.parity == 1; "
+            "assert a.full is False and a.dump_outputs is None; "  # a plain run: the headline alone, nothing written
             "print('ok')" % REPO)
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and "ok" in p.stdout, p.stderr[-2000:]

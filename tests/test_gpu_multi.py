@@ -39,7 +39,7 @@ def test_bench_rccl_parity_multi_gpu(engine):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(N),
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", str(N),
            "--model", "resnet18", "--batch", "16", "--steps", "3", "--warmup", "2", "--engine", engine,
-           "--cpu-baseline", "0", "--collective-bench", "0"]
+           "--cpu-baseline", "0", "--collective-bench", "0", "--full"]
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]

@@ -21,7 +21,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--model", "resnet18", "--batch", "16", "--steps", "3", "--warmup", "2", "--cpu-baseline", "0"]
+# --full: these tests are about the legs after the timed region (a plain run ends with the headline)
+SMALL = ["--model", "resnet18", "--batch", "16", "--steps", "3", "--warmup", "2", "--cpu-baseline", "0", "--full"]
 NO_LEGS = ["--zero-leg", "0", "--colossal-leg", "0"]  # configs[3] / [4] legs: on by default
 
 
@@ -221,6 +222,48 @@ def test_bench_n1_contract(cuda_device):
     # configs[4] on torch alone in the same run (torch DDP + GradScaler + fused AdamW)
     assert c["torch"]["images_per_sec"] > 0 and c["torch"]["steps"] > 0
     assert abs(c["vs_torch"] - c["images_per_sec"] / c["torch"]["images_per_sec"]) < 1e-9
+
+
+def test_bench_plain_run_headline_only_and_dump(cuda_device, tmp_path):
+    """Without --full: the timed steps and the line, no leg after them; --dump-outputs
+    writes the loss, updated parameters and buffers of one more step from the initial state as
+    float32 .npy, the same in a second run."""
+    import numpy as np
+
+    plain = [a for a in SMALL if a != "--full"]
+    p = _run([sys.executable, "-u", "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / "dump")] + plain, _env())
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = _json_lines(p.stdout)
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["unit"] == "images/sec"
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16" and d["metric"].startswith("images/sec (node)")
+    assert abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    # the in-step roofline needs no run of its own: the timed steps' 3 update launches
+    assert d["roofline"]["launches"] == 3 and d["roofline"]["achieved"] > 0 and "frac_beyond_ic" not in d["roofline"]
+    assert d["parity"] is None and d["grad_sync_kernels"] is None and d["vs_baseline"] is None
+    for k in ("zero2", "colossal", "torch_ddp", "bucket_policy_ab", "cpu_baseline", "leg_seconds", "leg_errors"):
+        assert k not in d, k
+    assert "tail_ms" not in d["grad_sync"] and "standalone" not in d["grad_sync"]
+    files = {f: np.load(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")}
+    assert set(files) == {"loss.npy", "params.npy", "buffers.npy"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 2**20
+    # ResNet-18's 11.7 M parameters: the fixed sample of bench.DUMP_SAMPLE_ELEMS of them
+    assert files["params.npy"].shape == (min(d["config"]["params"], 8 * 1024 * 1024),) and files["loss.npy"].shape == (1,)
+    assert np.abs(files["params.npy"]).max() > 0
+    # a second run with the same arguments writes the same outputs: one step from the fixed initial
+    # state on the fixed batch.  MIOpen's kernels sum in no fixed order and every layer's activations
+    # and gradients are rounded to bf16 (8 significant bits), so a value may move by 2^-8 of its array's
+    # scale per layer it passed through, ResNet-18's 18 weight layers at the most (the end state of
+    # the timed steps themselves differed by about half its scale between two runs)
+    p2 = _run([sys.executable, "-u", "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / "dump2")] + plain, _env())
+    assert p2.returncode == 0, p2.stderr[-3000:]
+    for f, a in files.items():
+        b = np.load(tmp_path / "dump2" / f)
+        diff = float(np.abs(a.astype(np.float64) - b).max())
+        print(f, "max |a - b|", diff, "scale", float(np.abs(a).max()))
+        assert diff <= 18 * 2.0**-8 * np.abs(a).max(), (f, diff)
 
 
 def test_bench_n2_driver_launch_gloo_rehearsal(cuda_device):
