@@ -13,6 +13,9 @@ row also `batched_*`: the same launches back to back between one event pair):
   SGD momentum+wd     20 B/param    torch.optim.SGD foreach=True  step
   Adam                28 B/param    torch.optim.Adam foreach=True step
   sq-norm              4 B/param    torch._foreach_norm + stack/norm (clip_grad_norm_)
+  LARS norms           8 B/param    torch._foreach_norm(params), torch._foreach_norm(grads)
+  LARS update         20 B/param    (timed in-step, right behind its norms pass)
+  LARS step           28 B/param    the two norms + trust ratios + foreach add / mul_ / add_ / mul / add_
 
 Working sets are replicated `--replicas` times so the timed data exceeds the
 256 MiB Infinity Cache (true HBM rates).  Prints one JSON object per kernel.
@@ -34,16 +37,17 @@ HBM_PEAK = 8000.0
 _LAST = {}
 
 
-def timeit_plan(plan, fn, iters=20, warmup=3):
+def timeit_plan(plan, fn, iters=20, warmup=3, kind=None, per=1):
     """libgsync launches: the plan launch timer (HIP events recorded by the
-    library right around each kernel on its stream)."""
+    library right around each kernel on its stream).  `fn` makes `per` timed
+    launches; `kind` keeps the records of one GS_OP_* kind."""
     _LAST["fn"] = fn
     for _ in range(warmup):
         fn()
-    plan.timer_enable(iters)
+    plan.timer_enable(iters * per)
     for _ in range(iters):
         fn()
-    ts = sorted(plan.timer_read())
+    ts = sorted(plan.timer_read(kind=kind))
     plan.timer_enable(0)
     return ts[len(ts) // 2], sum(ts) / len(ts)
 
@@ -133,6 +137,25 @@ def main():
     plan.set_ptrs(2, bufs)
     rec("sgd_momentum_wd", 20 * n, *timeit_plan(plan, lambda: plan.sgd(torch.float32, 1e-6, 0.9, 0.0, 1e-4, False, False, False),
                                                 args.iters), "libgsync")
+    # LARS (FusedLARS's two launches; 1-D tensors unadapted, as its default): the norms
+    # alone, the update as it runs in a step (right behind the norms pass that read the
+    # same p and g), and the pair
+    from distributed_training_amd import _lib as L
+
+    plan.set_adapt([len(s) > 1 for s in shapes])
+    nrm = torch.zeros(2 * len(shapes), device=dev)
+    lars_args = (torch.float32, 1e-6, 0.9, 1e-4, 1e-3, 1e-8, nrm)
+
+    def lars_step():
+        plan.lars_norms(torch.float32, nrm)
+        plan.lars(*lars_args)
+
+    rec("lars_norms", 8 * n, *timeit_plan(plan, lambda: plan.lars_norms(torch.float32, nrm), args.iters), "libgsync")
+    upd = timeit_plan(plan, lars_step, args.iters, kind=L.GS_OP_LARS, per=2)
+    _LAST.pop("fn")  # the update is not launched alone: no batched figure for it
+    rec("lars_update", 20 * n, *upd, "libgsync")
+    both = timeit(lars_step, args.iters)  # one event pair around the two launches
+    rec("lars_step", 28 * n, *both, "libgsync")
     plan.set_ptrs(2, ms)
     plan.set_ptrs(3, vs)
     rec("adam", 28 * n, *timeit_plan(plan, lambda: plan.adam(torch.float32, 1e-6, 0.9, 0.999, 1e-8, 0.0, False, False, -1e-6, 0.5),
@@ -157,6 +180,24 @@ def main():
         rec("unpack_f32", 8 * n, *timeit(t_unpack, args.iters), "torch per-param (Reducer)")
         rec("sqnorm_f32", 4 * n, *timeit(lambda: torch.linalg.vector_norm(torch.stack(torch._foreach_norm(grads))),
                                          args.iters), "torch _foreach_norm")
+        # a LARS step as torch foreach ops, everything on the device (no host sync)
+        lp, lb = [p.clone() for p in params], [b.clone() for b in bufs]
+        l_adapt = torch.tensor([len(s) > 1 for s in shapes], device=dev)
+
+        def t_lars_norms():
+            return torch._foreach_norm(lp), torch._foreach_norm(grads)
+
+        def t_lars():
+            wn, gn = (torch.stack(x) for x in t_lars_norms())
+            ratio = torch.where(l_adapt & (wn > 0) & (gn > 0), 1e-3 * wn / (gn + 1e-4 * wn + 1e-8), 1.0)
+            wds = (l_adapt * 1e-4).unbind()
+            g2 = torch._foreach_add(grads, torch._foreach_mul(lp, wds))
+            torch._foreach_mul_(lb, 0.9)
+            torch._foreach_add_(lb, g2)
+            torch._foreach_add_(lp, torch._foreach_mul(lb, (ratio * -1e-6).unbind()))
+
+        rec("lars_norms", 8 * n, *timeit(t_lars_norms, args.iters), "torch _foreach_norm x2")
+        rec("lars_step", 28 * n, *timeit(t_lars, args.iters), "torch foreach composition")
         ps = [torch.nn.Parameter(p.clone()) for p in params]
         for p, gr in zip(ps, grads):
             p.grad = gr

@@ -139,6 +139,32 @@ struct AdamHyper {
   float b2, w1, w2, eps, wd, step_size, bc2s, decay;  // w1 = float(1-b1), decay = float(1-lr*wd)
   int adamw, maximize;
 };
+// LARS (gs_lars_step): eta = the trust coefficient
+struct LarsHyper {
+  float lr, mom, wd, eta, eps;
+};
+// The per-tensor learning rate and weight decay of LARS from the tensor's Σp², Σg²
+// (include/gsync.h, gs_lars_step): every multiply and add rounded once, no fma; the
+// same expression on the host and the device (IEEE sqrt and division on both).
+// m: the grad multiplier (has_m), which scales ‖g‖ as it scales every g.
+#ifdef __HIPCC__
+#define GS_HD_INL __host__ __device__ inline
+#else
+#define GS_HD_INL inline
+#endif
+GS_HD_INL void lars_coef(const LarsHyper& h, float sp, float sg, int adapt, bool has_m, float m, float* slr,
+                         float* wd) {
+  float ratio = 1.f;
+  *wd = 0.f;
+  if (adapt != 0) {
+    *wd = h.wd;
+    const float wn = sqrtf(sp);
+    float gn = sqrtf(sg);
+    if (has_m) gn = gn * m;
+    if (wn > 0.f && gn > 0.f) ratio = (h.eta * wn) / ((gn + h.wd * wn) + h.eps);
+  }
+  *slr = h.lr * ratio;
+}
 // Gradient-norm clip folded into an update launch (gs_plan_set_clip): the
 // update's workgroups form the coefficient themselves, so no coefficient
 // launch (and, with the plan's own group sums, no combine launch) sits between
@@ -221,6 +247,12 @@ struct gs_plan {
   bool grads_read = false;      // a Σg² pass read slot 1 since the last update (load policy)
   int read_hint = 0;            // Σg² loads: 0 the size rule, 1 non-temporal, 2 cached (gs_plan_set_read_hint)
   float h_red = 0.f;            // host plans: the Σg² of gs_sqnorm_partial
+  // LARS (gs_lars_norms / gs_lars_step): the per-tensor adaptation flags (empty = all 1)
+  // and, on HIP plans, the segmented reduction's scratch, allocated on first use:
+  // d_lars = chunk slot bases | per-tensor [first slot, count] | adapt | partial slots
+  std::vector<int32_t> adapt;
+  void* d_lars = nullptr;
+  int64_t lars_slots = 0;
   // launch timer ring (gs_plan_timer_enable)
   std::vector<void*> timer_ev;  // [2 * slots]: start, stop
   std::vector<int32_t> timer_kind;  // [slots]: GS_OP_* of the timed launch
@@ -320,6 +352,10 @@ int hip_sgd(gs_plan* p, int gdt, int ldt, const SgdHyper& h, const float* gs, co
             const ClipArgs* clip, void* stream);
 int hip_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gs, const float* fi,
              const ClipArgs* clip, void* stream);
+int hip_lars_set_adapt(gs_plan* p);  // upload p->adapt (allocates the LARS scratch on first use)
+int hip_lars_norms(gs_plan* p, int gdt, float* norms, void* stream);
+int hip_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gs, const float* fi,
+             void* stream);
 int hip_device_count();
 int hip_memset_async(void* dst, int value, size_t bytes, void* stream);
 int hip_stream_wait(void* waiter, void* signaler);
@@ -339,6 +375,8 @@ int host_sgd(gs_plan* p, int gdt, int ldt, const SgdHyper& h, const float* gs, c
              const ClipArgs* clip);
 int host_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gs, const float* fi,
               const ClipArgs* clip);
+int host_lars_norms(gs_plan* p, int gdt, float* norms);
+int host_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gs, const float* fi);
 // the clip coefficient of ClipArgs on the host (groups == 0: *sq is final)
 float host_clip_factor(const ClipArgs& c, const float* gs);
 // the device's 64-lane DPP fold (gs_kernels.hip wave_reduce) restated on the

@@ -443,7 +443,7 @@ __device__ __forceinline__ TV load_tv(const Op& op, const PlanArgs& P, int t) {
   v.align = bits;
   v.numel = SCALAR ? cload(P.numel, t) : P.numel[t];
   v.off = SCALAR ? cload(P.off, t) : P.off[t];
-  v.pad = 0;
+  v.pad = t;  // the tensor's index (LarsOp reads its per-tensor norms and flag by it)
   return v;
 }
 
@@ -1040,6 +1040,63 @@ struct SgdOp {
   }
 };
 
+// LARS (gs_lars_step): slots 0 = p (f32), 1 = g (GD), 2 = momentum buffer (f32).  SGD with
+// momentum whose learning rate and weight decay are per tensor: every lane forms its
+// tensor's (slr, wd) from the tensor's Σp², Σg² (gs_lars_norms) and adaptation flag —
+// on the full-chunk path the tensor index is wave-uniform, so that is a handful of
+// scalar loads and one sqrt / division pair per group of chunks, and no coefficient
+// launch sits between the norms and the update.  No fma anywhere: the contract
+// (include/gsync.h) rounds every multiply and add once.
+// NTG: non-temporal loads of the grad (false right behind gs_lars_norms when it fits the cache)
+template <int N, int GD, bool NTG = false>
+struct LarsOp {
+  static constexpr int kN = N;
+  static constexpr int kG = GS_G_SGD;
+  static constexpr int kRed = 0;
+  static constexpr int kRedGrid = kGridLimit;
+  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
+  static constexpr int kKind = GS_OP_LARS;
+  float* partials = nullptr;
+  LarsHyper h;
+  const float* norms;            // [2n]: Σp², Σg² per tensor
+  const int32_t* adapt;          // [n]
+  const float* gscale;
+  const float* found_inf;
+  const float* hyper = nullptr;  // [lr] in device memory (gs_plan_set_hyper_source)
+  bool use_gs = false;           // the grad multiplier gsv applies (set by load_hyper)
+  float gsv = 1.f;
+  struct Frag { float p[N], g[N], b[N], slr, wd; };
+  __device__ int phys(int k) const { return k; }
+  __device__ bool active() const { return found_inf == nullptr || *found_inf == 0.f; }
+  __device__ bool fast_ok(const TV& v) const { return v.vec(0) && v.vec(1) && (h.mom == 0.f || v.vec(2)); }
+  template <bool F>
+  __device__ void load(const TV& v, int64_t e0, uint32_t lo, Frag& f) const {
+    ld<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.p);
+    ld<GD, N, F, NTG>(v.ptr[1], e0, lo, v.numel, v.vec(1), f.g);
+    if (h.mom != 0.f) ld<GS_F32, N, F>(v.ptr[2], e0, lo, v.numel, v.vec(2), f.b);
+    const int t = v.pad;
+    lars_coef(h, norms[2 * t], norms[2 * t + 1], adapt[t], use_gs, gsv, &f.slr, &f.wd);
+  }
+  template <bool F>
+  __device__ void apply(const TV& v, int64_t e0, uint32_t lo, Frag& f, float&) const {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      float g = f.g[i];
+      if (use_gs) g = g * gsv;
+      if (f.wd != 0.f) g = g + f.wd * f.p[i];
+      float d = g;
+      if (h.mom != 0.f) {
+        const float b = f.b[i] * h.mom + g;
+        f.b[i] = b;
+        d = b;
+      }
+      f.p[i] = f.p[i] - f.slr * d;
+    }
+    st<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.p);
+    if (h.mom != 0.f) st<GS_F32, N, F>(v.ptr[2], e0, lo, v.numel, v.vec(2), f.b);
+  }
+};
+
 // Adam/AdamW: slots 0 = p, 1 = g, 2 = exp_avg, 3 = exp_avg_sq, 4 = low-precision copy
 template <int N, int GD, int LD, bool NTG = true>
 struct AdamOp {
@@ -1165,6 +1222,12 @@ __device__ __forceinline__ void load_hyper(SgdOp<N, GD, LD, NTG>& op) {
     if (op.h.first < 0) op.h.first = op.hyper[1] != 0.f;  // device first-step flag (AMP skips)
   }
   load_grad_multiplier(op);
+}
+template <int N, int GD, bool NTG>
+__device__ __forceinline__ void load_hyper(LarsOp<N, GD, NTG>& op) {
+  if (op.hyper) op.h.lr = op.hyper[0];
+  op.use_gs = op.gscale != nullptr;
+  op.gsv = op.gscale ? *op.gscale : 1.f;
 }
 template <int N, int GD, int LD, bool NTG>
 __device__ __forceinline__ void load_hyper(AdamOp<N, GD, LD, NTG>& op) {

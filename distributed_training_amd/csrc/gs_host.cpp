@@ -379,6 +379,66 @@ int host_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gsc
   return GS_OK;
 }
 
+// LARS on the host (include/gsync.h, gs_lars_step): the same contract as the device
+// kernels — fp32, every multiply and add rounded once, no fma.  The per-tensor sums
+// run in element order, 1 Ki-element blocks folded front to back: a fixed order
+// (serial, so the thread count does not enter), not the device's.
+int host_lars_norms(gs_plan* p, int gdt, float* norms) {
+  constexpr int64_t kBlk = 1024;
+  GS_HOST_FLOAT(gdt, GD, {
+    for (int t = 0; t < p->n; ++t) {
+      const float* pp = static_cast<const float*>(slot(p, 0, t));
+      const void* gp = slot(p, 1, t);
+      float sp = 0.f, sg = 0.f;
+      for (int64_t i0 = 0; i0 < p->numel[t]; i0 += kBlk) {
+        const int64_t i1 = std::min(p->numel[t], i0 + kBlk);
+        float bp = 0.f, bg = 0.f;
+        for (int64_t i = i0; i < i1; ++i) {
+          const float x = pp[i], g = ldT<GD>(gp, i);
+          bp = bp + x * x;
+          bg = bg + g * g;
+        }
+        sp = sp + bp;
+        sg = sg + bg;
+      }
+      norms[2 * t] = sp;
+      norms[2 * t + 1] = sg;
+    }
+  });
+  return GS_OK;
+}
+
+int host_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gsc, const float* fi) {
+  GS_TRY_RET(check_float(gdt));
+  if (fi && fi[0] != 0.f) return GS_OK;
+  const bool has_m = gsc != nullptr;
+  const float m = gsc ? gsc[0] : 1.f;
+  std::vector<float> slr(p->n), wdt(p->n);
+  for (int t = 0; t < p->n; ++t)
+    lars_coef(h, norms[2 * t], norms[2 * t + 1], p->adapt.empty() ? 1 : p->adapt[t], has_m, m, &slr[t], &wdt[t]);
+  GS_HOST_FLOAT(gdt, GD, {
+    for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
+      float* pp = static_cast<float*>(slot(p, 0, t));
+      const void* gp = slot(p, 1, t);
+      float* bp = static_cast<float*>(slot(p, 2, t));
+      const float lr_t = slr[t], wd_t = wdt[t];
+      for (int64_t i = i0; i < i1; ++i) {
+        float g = ldT<GD>(gp, i);
+        if (has_m) g = g * m;
+        if (wd_t != 0.f) g = g + wd_t * pp[i];
+        float d = g;
+        if (h.mom != 0.f) {
+          const float b = bp[i] * h.mom + g;
+          bp[i] = b;
+          d = b;
+        }
+        pp[i] = pp[i] - lr_t * d;
+      }
+    });
+  });
+  return GS_OK;
+}
+
 }  // namespace gs
 
 extern "C" int gs_set_host_threads(int n) {

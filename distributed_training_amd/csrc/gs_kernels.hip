@@ -139,6 +139,7 @@ int hip_plan_release(gs_plan* p) {
   if (p->d_static) (void)hipFree(p->d_static);
   if (p->d_table) (void)hipFree(p->d_table);
   if (p->d_partials) (void)hipFree(p->d_partials);
+  if (p->d_lars) (void)hipFree(p->d_lars);  // the LARS scratch, if a gs_lars_* call made one
   if (p->pinned) (void)hipHostFree(p->pinned);
   return GS_OK;
 }

@@ -533,6 +533,57 @@ int gs_adam_step(gs_plan* p, int grad_dtype, int lowp_dtype, double lr, double b
   return hip_adam(p, grad_dtype, lowp_dtype, h, grad_scale_dev, found_inf_dev, clip, stream);
 }
 
+int gs_plan_set_adapt(gs_plan* p, const int32_t* adapt) {
+  PLAN_OK(p);
+  GS_CHECK_ARG(p->n == 0 || adapt != nullptr, "gs_plan_set_adapt: NULL flags");
+  p->adapt.assign(adapt, adapt + p->n);
+  if (p->kind == GS_DEV_HIP) return hip_lars_set_adapt(p);
+  return GS_OK;
+}
+
+// slots 0 .. n_slots-1 of every non-empty tensor are bound
+static int lars_slots_bound(const gs_plan* p, int n_slots, const char* who) {
+  for (int s = 0; s < n_slots; ++s)
+    for (int t = 0; t < p->n; ++t)
+      if (p->numel[t] > 0 && p->h_ptrs[static_cast<size_t>(s) * p->n + t] == nullptr)
+        return fail(GS_EINVAL, std::string(who) + ": slot " + std::to_string(s) + " of tensor " +
+                                   std::to_string(t) + " is not bound");
+  return GS_OK;
+}
+
+int gs_lars_norms(gs_plan* p, int grad_dtype, float* norms_out, void* stream) {
+  GsRange range("gs_lars_norms");
+  PLAN_OK(p);
+  GS_CHECK_ARG(is_float_dtype(grad_dtype), "gs_lars_norms: grad dtype must be f32, bf16 or f16");
+  GS_CHECK_ARG(p->n == 0 || norms_out != nullptr, "gs_lars_norms: NULL output");
+  GS_TRY_RET(lars_slots_bound(p, 2, "gs_lars_norms"));
+  p->grads_read = true;  // the update right behind re-reads the grads: cached loads when they fit
+  if (p->kind == GS_DEV_HOST) return host_lars_norms(p, grad_dtype, norms_out);
+  return hip_lars_norms(p, grad_dtype, norms_out, stream);
+}
+
+int gs_lars_step(gs_plan* p, int grad_dtype, double lr, double momentum, double weight_decay,
+                 double trust_coefficient, double eps, const float* norms, const float* grad_scale_dev,
+                 const float* found_inf_dev, void* stream) {
+  GsRange range("gs_lars_step");
+  PLAN_OK(p);
+  GS_CHECK_ARG(is_float_dtype(grad_dtype), "gs_lars_step: grad dtype must be f32, bf16 or f16");
+  GS_CHECK_ARG(p->n == 0 || norms != nullptr, "gs_lars_step: NULL norms");
+  GS_CHECK_ARG(momentum >= 0 && weight_decay >= 0 && trust_coefficient >= 0 && eps >= 0,
+               "gs_lars_step: momentum, weight_decay, trust_coefficient and eps must be >= 0");
+  if (p->clip_on)
+    return fail(GS_ESTATE, "gs_lars_step: a gradient-norm clip is set on the plan (gs_plan_set_clip); "
+                           "clipping is not part of LARS");
+  LarsHyper h{static_cast<float>(lr), static_cast<float>(momentum), static_cast<float>(weight_decay),
+              static_cast<float>(trust_coefficient), static_cast<float>(eps)};
+  GS_TRY_RET(lars_slots_bound(p, h.mom != 0.f ? 3 : 2, "gs_lars_step"));
+  if (p->kind == GS_DEV_HOST) {
+    if (p->hyper) h.lr = p->hyper[0];
+    return host_lars(p, grad_dtype, h, norms, grad_scale_dev, found_inf_dev);
+  }
+  return hip_lars(p, grad_dtype, h, norms, grad_scale_dev, found_inf_dev, stream);
+}
+
 int gs_plan_set_hyper_source(gs_plan* p, const float* hyper) {
   PLAN_OK(p);
   p->hyper = hyper;

@@ -254,6 +254,46 @@ class TensorListPlan:
             "gs_sgd_step",
         )
 
+    # ------------------------------------------------------------------ LARS
+    def _where_plan(self, t: torch.Tensor) -> bool:
+        return (t.device.type == "cuda") == (self.kind == L.GS_DEV_HIP)
+
+    def set_adapt(self, flags):
+        """Per-tensor LARS adaptation flags (gs_plan_set_adapt; default all on):
+        tensor t gets the trust ratio and weight decay only where flags[t] is
+        true.  Static for the plan; call it outside a capture (on a GPU plan it
+        also allocates the plan's LARS scratch)."""
+        flags = [int(bool(f)) for f in flags]
+        if len(flags) != self.n:
+            raise ValueError(f"plan has {self.n} tensors, got {len(flags)} flags")
+        L.check(L.lib().gs_plan_set_adapt(self.handle, L.i32_array(flags)), "gs_plan_set_adapt")
+
+    def _norms_ok(self, norms: torch.Tensor):
+        if norms.dtype != torch.float32 or not norms.is_contiguous() or norms.numel() < 2 * self.n or \
+                not self._where_plan(norms):
+            raise ValueError(f"LARS norms: contiguous fp32[>= {2 * self.n}] where the plan runs")
+
+    def lars_norms(self, grad_dtype, out: torch.Tensor, stream=None):
+        """out[2t] = Σp², out[2t+1] = Σg² of tensor t (slot 0 = params, slot 1 =
+        grads), in an order the plan alone fixes (gs_lars_norms)."""
+        self._norms_ok(out)
+        L.check(L.lib().gs_lars_norms(self.handle, L.gs_dtype(grad_dtype), out.data_ptr(), self._stream(stream)),
+                "gs_lars_norms")
+
+    def lars(self, grad_dtype, lr, momentum, weight_decay, trust_coefficient, eps, norms: torch.Tensor,
+             grad_scale=None, found_inf=None, stream=None):
+        """The LARS update on slots 0 = p, 1 = g, 2 = momentum buffer with the
+        per-tensor sums of :meth:`lars_norms` (gs_lars_step)."""
+        self._norms_ok(norms)
+        L.check(
+            L.lib().gs_lars_step(
+                self.handle, L.gs_dtype(grad_dtype), float(lr), float(momentum), float(weight_decay),
+                float(trust_coefficient), float(eps), norms.data_ptr(),
+                None if grad_scale is None else grad_scale.data_ptr(),
+                None if found_inf is None else found_inf.data_ptr(), self._stream(stream)),
+            "gs_lars_step",
+        )
+
     def adam(self, grad_dtype, lr, beta1, beta2, eps, weight_decay, adamw, maximize, step_size,
              bias_correction2_sqrt, lowp_dtype=None, grad_scale=None, found_inf=None, stream=None):
         L.check(

@@ -7,6 +7,11 @@
   (T:optim/adam.py:554-800 ``_multi_tensor_adam``, the reference's default on
   GPU, ``R:resnet/pytorch_ddp/ddp_train.py:97``): one pass over
   (p, g, m, v) = 28 B/param instead of the ~72 B/param of 7 foreach passes.
+* :class:`FusedLARS` — layer-wise adaptive SGD for large global batches (no
+  torch counterpart; the arithmetic is ``include/gsync.h``'s contract): the
+  per-tensor ‖w‖², ‖g‖² of the whole list in one deterministic pass
+  (8 B/param), then one update pass (20 B/param) that forms each tensor's trust
+  ratio itself.
 * :func:`clip_grad_norm_` — ``torch.nn.utils.clip_grad_norm_``
   (T:nn/utils/clip_grad.py:50-186) with a wave-level Σg² reduction and the
   clip coefficient kept on the device (no host sync).
@@ -357,6 +362,132 @@ class FusedSGD(_FusedBase):
                     flag.mul_(self.found_inf)  # kept only when the step was skipped
                 else:
                     flag.zero_()
+        return loss
+
+
+class FusedLARS(_FusedBase):
+    """LARS (You et al. 2017; the MLPerf ResNet-50 large-batch optimizer): SGD
+    with momentum whose learning rate is multiplied, per tensor, by the trust
+    ratio ``trust_coefficient * ‖w‖ / (‖g‖ + weight_decay * ‖w‖ + eps)``.
+
+    Two kernels per (param group, grad dtype): the per-tensor Σp², Σg² of the
+    whole list in one pass (``gs_lars_norms``, 8 B/param), then the update
+    (``gs_lars_step``, 20 B/param) whose workgroups form their tensor's ratio
+    themselves — instead of two ``torch.norm`` per parameter plus the foreach
+    update.  The per-tensor sums are deterministic (an order the parameter list
+    alone fixes), so data-parallel replicas that hold the same averaged grads
+    stay bit-identical.  There is no torch LARS to match: the arithmetic is the
+    contract in ``include/gsync.h`` (fp32, every multiply and add rounded once)::
+
+        wn = sqrt(Σp²); gn = sqrt(Σg²) (* grad_scale)
+        adapted:    wd_t = wd; ratio = (eta*wn) / ((gn + wd*wn) + eps) if wn > 0 and gn > 0 else 1
+        unadapted:  wd_t = 0;  ratio = 1
+        g = g (* grad_scale) (+ wd_t*p); buf = buf*momentum + g; p = p - (lr*ratio)*buf
+
+    The param-group key ``adapt`` chooses the adapted tensors: ``None``
+    (default) those with ``p.ndim > 1`` — biases and BatchNorm weights get
+    neither the trust ratio nor weight decay — ``True`` all, ``False`` none.
+    Parameters are fp32 and dense; grads fp32, bf16 or fp16; a parameter whose
+    grad is None is skipped.  State is ``momentum_buffer`` (torch SGD's key),
+    created as zeros.  ``grad_scale`` / ``found_inf`` behave as in the other
+    fused optimizers (``amp.GradScaler`` drives it unchanged), and
+    ``capturable=True`` with :meth:`refresh_hyper` lets ``graphs.CapturedStep``
+    record it (take one eager step first: state and scratch must exist).
+
+    Out of scope: ZeRO shards (a tensor's norm would span ranks),
+    ``max_grad_norm``, nesterov, ``DDP._register_fused_optim``.
+    """
+
+    def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=0.0, trust_coefficient=1e-3, eps=1e-8,
+                 *, capturable=False):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if trust_coefficient < 0.0:
+            raise ValueError(f"Invalid trust_coefficient value: {trust_coefficient}")
+        if eps < 0.0:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, trust_coefficient=trust_coefficient,
+                        eps=eps, adapt=None, capturable=bool(capturable))
+        super().__init__(params, defaults)
+        self._last_norms: list = []
+
+    def kernel_ms(self) -> list:
+        """Durations (ms) of the norm passes and the updates since the last call, all plans."""
+        kinds = (L.GS_OP_LARS_NORM, L.GS_OP_LARS)
+        return [ms for plan in self._plans.plans() if plan.kind == L.GS_DEV_HIP
+                for k, v in plan.timer_read_by_kind().items() if k in kinds for ms in v]
+
+    def sq_norms(self) -> list:
+        """[(params, norms)] per plan of the last step: ``norms`` is the fp32[2n]
+        tensor the step published, [2t] = Σp², [2t+1] = Σg² of ``params[t]``
+        (of the values before the update; overwritten by the next step)."""
+        return list(self._last_norms)
+
+    def _collect(self, group):
+        out = {}  # grad dtype -> lists
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if p.grad.is_sparse:
+                raise RuntimeError("FusedLARS does not support sparse gradients")
+            _check_dense(p, p.grad, "FusedLARS", self._dense_seen)
+            if p.dtype != torch.float32:
+                raise RuntimeError("FusedLARS expects fp32 parameters (keep a fp32 master copy)")
+            buf = None
+            if group["momentum"] != 0:
+                st = self.state[p]
+                buf = st.get("momentum_buffer")
+                if buf is None:
+                    if _capturing():
+                        raise RuntimeError("FusedLARS: momentum buffers must exist before capture "
+                                           "(take an eager step first)")
+                    buf = st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            ps, gs, bs = out.setdefault(p.grad.dtype, ([], [], []))
+            ps.append(p)
+            gs.append(p.grad)
+            bs.append(buf)
+        return out
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        dev_state = self._device_state()
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            for gdt, (ps, gs, bs) in self._collect(group).items():
+                plan = self._plans.get(ps)
+                plan.set_ptrs(0, ps)
+                plan.set_ptrs(1, gs)
+                if group["momentum"] != 0:
+                    plan.set_ptrs(2, bs)
+                adapt = group.get("adapt")
+                flags = tuple((p.ndim > 1) if adapt is None else bool(adapt) for p in ps)
+                if getattr(plan, "_adapt", None) != flags:
+                    if _capturing():
+                        raise RuntimeError("FusedLARS: take one eager step before capturing "
+                                           "(the plan's adaptation flags and scratch are set there)")
+                    plan.set_adapt(flags)
+                    plan._adapt = flags
+                    plan._lars_norms = torch.zeros(2 * len(ps), dtype=torch.float32, device=ps[0].device)
+                if dev_state:
+                    h = self._group_hyper(gi, group, ps[0].device)
+                    if getattr(plan, "_hyper", None) is not h["hyper"]:
+                        plan.set_hyper_source(h["hyper"])
+                work.append((group, plan, gdt, ps))
+        if dev_state:
+            self.refresh_hyper()
+        self._last_norms = [(ps, plan._lars_norms) for _, plan, _, ps in work]
+        for group, plan, gdt, ps in work:
+            plan.lars_norms(gdt, plan._lars_norms)
+            plan.lars(gdt, group["lr"], group["momentum"], group["weight_decay"], group["trust_coefficient"],
+                      group["eps"], plan._lars_norms, grad_scale=self.grad_scale, found_inf=self.found_inf)
         return loss
 
 

@@ -204,6 +204,8 @@ int64_t gs_plan_task_units(gs_plan* p);
 #define GS_OP_SGD 6
 #define GS_OP_ADAM 7
 #define GS_OP_SUM 8
+#define GS_OP_LARS_NORM 9 /* gs_lars_norms: the segmented reduction and its finishing kernel, one record */
+#define GS_OP_LARS 10
 int gs_plan_timer_enable(gs_plan* p, int n_slots);
 int gs_plan_timer_read(gs_plan* p, float* ms_out, int32_t* kind_out, int cap);
 /* register the per-tensor pointers of one slot (uploads on change, ordered on `stream`) */
@@ -337,6 +339,63 @@ int gs_adam_step(gs_plan* p, int grad_dtype, int lowp_dtype, double lr, double b
                  double beta2, double eps, double weight_decay, int adamw, int maximize,
                  double step_size, double bias_correction2_sqrt, const float* grad_scale_dev,
                  const float* found_inf_dev, void* stream);
+/* LARS (You et al. 2017, layer-wise adaptive rate scaling; the MLPerf ResNet-50
+ * large-batch optimizer): SGD with momentum whose learning rate is multiplied,
+ * per tensor, by the trust ratio eta*‖w‖ / (‖g‖ + wd*‖w‖).  Three entry points:
+ * the per-tensor adaptation flags, the per-tensor Σp² / Σg² (one pass over slots
+ * 0 and 1, 8 B/param with fp32 grads), and the update (one pass over p, g, buf,
+ * 20 B/param), each update workgroup forming its tensor's ratio itself.
+ *
+ * Arithmetic (all fp32; every multiply and add rounded once, NO fma, so a
+ * float32 restatement is exact op for op).  Per tensor t:
+ *   sp = Σ p_i*p_i   sg = Σ g_i*g_i    (g converted from grad_dtype, before any
+ *                                       multiplier; fp32 sums in the plan's fixed order)
+ *   wn = sqrt(sp)    gn = sqrt(sg);    if grad_scale_dev (m = *grad_scale_dev): gn = gn*m
+ *   adapt[t] != 0:  wd_t = wd; ratio = (wn > 0 && gn > 0) ? (eta*wn) / ((gn + wd*wn) + eps) : 1
+ *   adapt[t] == 0:  wd_t = 0;  ratio = 1
+ *   slr = lr * ratio
+ * per element:
+ *   g = g_i; if (m) g = g*m; if (wd_t != 0) g = g + wd_t*p
+ *   mom != 0: b = b*mom + g; d = b    (the buffer starts as zeros: no first-step branch)
+ *   mom == 0: d = g                   (slot 2 is not touched)
+ *   p = p - slr*d
+ * sqrt and / are the correctly rounded IEEE forms; m is assumed positive (an AMP
+ * inverse scale); non-finite norms get no special handling.  A tensor of 0
+ * elements has sums of 0 and is otherwise untouched.
+ *
+ * Determinism: the per-tensor sums are formed in an order fixed by the plan alone
+ * (one partial per (1 Ki-element chunk, tensor) pair, a fixed tree inside it, then
+ * a fixed fold of the tensor's partials) — no floating-point atomics, nothing
+ * that depends on the grid or on arrival order — so data-parallel replicas that
+ * hold the same averaged grads form the same ratios and stay bit-identical.  The
+ * host backend's order is fixed too (element order) but is not the device's.
+ *
+ * Not part of LARS here: gradient-norm clipping (a clip set on the plan is
+ * GS_ESTATE), nesterov, low-precision parameter copies, sharded tensors (a ZeRO
+ * shard's norm would span ranks).
+ *
+ * gs_plan_set_adapt: per-tensor adaptation flags (int32[n], host memory), static
+ * for the plan; default all 1.  Not capturable (it uploads synchronously); on a
+ * HIP plan it also allocates the plan's LARS scratch, which otherwise happens at
+ * the first gs_lars_norms (plans that never call either pay nothing).
+ * replaces: the `if p.ndim > 1` / exclude-list test of a Python LARS loop */
+int gs_plan_set_adapt(gs_plan* p, const int32_t* adapt);
+/* norms_out: fp32[2*n] in the plan's memory kind: [2t] = Σp², [2t+1] = Σg² of tensor t
+ * (slot 0 = params, fp32; slot 1 = grads, grad_dtype).  Two launches (the chunk pass,
+ * the per-tensor fold), no host sync; recordable into a hipGraph once the scratch exists.
+ * replaces: the per-parameter torch.norm(p), torch.norm(p.grad) pair of a Python
+ *           LARS (torch._foreach_norm x 2: T:nn/utils/clip_grad.py:96 is its only
+ *           fused form, and that collapses to one scalar) */
+int gs_lars_norms(gs_plan* p, int grad_dtype, float* norms_out, void* stream);
+/* the update above; slots: 0 = param (f32), 1 = grad (grad_dtype), 2 = momentum
+ * buffer (f32, unused if momentum == 0).  norms: gs_lars_norms' output for these
+ * p and g.  found_inf_dev (nullable): *found_inf != 0 writes nothing.  With a
+ * hyper source on the plan (gs_plan_set_hyper_source) lr is hyper[0], as for SGD.
+ * replaces: the foreach update of a Python LARS (per parameter: trust ratio,
+ *           grad.add(p, alpha=wd), buf.mul_(mom).add_(g), p.add_(buf, alpha=-lr*ratio)) */
+int gs_lars_step(gs_plan* p, int grad_dtype, double lr, double momentum, double weight_decay,
+                 double trust_coefficient, double eps, const float* norms,
+                 const float* grad_scale_dev, const float* found_inf_dev, void* stream);
 /* Step-varying hyper-parameters from memory instead of the arguments: with a
  * non-NULL source, every later gs_sgd_step / gs_adam_step on this plan reads
  *   SGD:  hyper[0] = lr; hyper[1] = "first step" flag (buf = g) when gs_sgd_step
