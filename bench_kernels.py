@@ -16,6 +16,9 @@ row also `batched_*`: the same launches back to back between one event pair):
   LARS norms           8 B/param    torch._foreach_norm(params), torch._foreach_norm(grads)
   LARS update         20 B/param    (timed in-step, right behind its norms pass)
   LARS step           28 B/param    the two norms + trust ratios + foreach add / mul_ / add_ / mul / add_
+  LAMB moments        24 B/param    (p, g, m, v read; m, v written; per-tensor sums of p^2, u^2)
+  LAMB update         16 B/param    (timed in-step, right behind its moments pass)
+  LAMB step           40 B/param    foreach lerp_ / mul_ / addcmul_ / sqrt / div / add + the two norms + ratios + add_
 
 Working sets are replicated `--replicas` times so the timed data exceeds the
 256 MiB Infinity Cache (true HBM rates).  Prints one JSON object per kernel.
@@ -86,6 +89,7 @@ def main():
     ap.add_argument("--replicas", type=int, default=1)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--skip-torch", action="store_true")
+    ap.add_argument("--only", default="", help="comma-separated row-name prefixes to run (default: all rows)")
     ap.add_argument("--tag", default=os.environ.get("GSYNC_LIB", "libgsync").split("/")[-1])
     args = ap.parse_args()
     from distributed_training_amd.multi_tensor import TensorListPlan
@@ -105,6 +109,10 @@ def main():
     views = [flat[o:o + torch.Size(s).numel()].view(s) for o, s in zip(offs, shapes)]
     views16 = [flat16[o:o + torch.Size(s).numel()].view(s) for o, s in zip(offs, shapes)]
     out = []
+    only = [o for o in args.only.split(",") if o]
+
+    def want(*names):
+        return not only or any(nm.startswith(o) for nm in names for o in only)
 
     last_fn = _LAST
 
@@ -122,12 +130,15 @@ def main():
 
     plan.set_ptrs(1, grads)
     plan.set_ptrs(2, grads)
-    rec("pack_f32", 8 * n, *timeit_plan(plan, lambda: plan.pack(1, torch.float32, flat, 0.125, 1), args.iters), "libgsync")
-    rec("pack_f32_to_bf16", 6 * n, *timeit_plan(plan, lambda: plan.pack(1, torch.float32, flat16, 0.125, 1), args.iters), "libgsync")
-    rec("unpack_f32", 8 * n, *timeit_plan(plan, lambda: plan.unpack(flat, 2, torch.float32), args.iters), "libgsync")
+    if want("pack", "unpack_f32"):
+        rec("pack_f32", 8 * n, *timeit_plan(plan, lambda: plan.pack(1, torch.float32, flat, 0.125, 1), args.iters), "libgsync")
+        rec("pack_f32_to_bf16", 6 * n, *timeit_plan(plan, lambda: plan.pack(1, torch.float32, flat16, 0.125, 1), args.iters), "libgsync")
+        rec("unpack_f32", 8 * n, *timeit_plan(plan, lambda: plan.unpack(flat, 2, torch.float32), args.iters), "libgsync")
     sq = torch.zeros(1, device=dev)
-    rec("unpack_f32+sqnorm", 8 * n, *timeit_plan(plan, lambda: plan.unpack(flat, 2, torch.float32, sqnorm=sq), args.iters), "libgsync")
-    rec("sqnorm_f32", 4 * n, *timeit_plan(plan, lambda: plan.sqnorm(1, torch.float32, sq), args.iters), "libgsync")
+    if want("unpack_f32+sqnorm"):
+        rec("unpack_f32+sqnorm", 8 * n, *timeit_plan(plan, lambda: plan.unpack(flat, 2, torch.float32, sqnorm=sq), args.iters), "libgsync")
+    if want("sqnorm"):
+        rec("sqnorm_f32", 4 * n, *timeit_plan(plan, lambda: plan.sqnorm(1, torch.float32, sq), args.iters), "libgsync")
     # the update kernels run on an update plan, as FusedSGD / FusedAdam build it
     from distributed_training_amd.multi_tensor import update_task_units
 
@@ -135,8 +146,9 @@ def main():
     plan.set_ptrs(0, params)
     plan.set_ptrs(1, grads)
     plan.set_ptrs(2, bufs)
-    rec("sgd_momentum_wd", 20 * n, *timeit_plan(plan, lambda: plan.sgd(torch.float32, 1e-6, 0.9, 0.0, 1e-4, False, False, False),
-                                                args.iters), "libgsync")
+    if want("sgd"):
+        rec("sgd_momentum_wd", 20 * n, *timeit_plan(
+            plan, lambda: plan.sgd(torch.float32, 1e-6, 0.9, 0.0, 1e-4, False, False, False), args.iters), "libgsync")
     # LARS (FusedLARS's two launches; 1-D tensors unadapted, as its default): the norms
     # alone, the update as it runs in a step (right behind the norms pass that read the
     # same p and g), and the pair
@@ -150,17 +162,60 @@ def main():
         plan.lars_norms(torch.float32, nrm)
         plan.lars(*lars_args)
 
-    rec("lars_norms", 8 * n, *timeit_plan(plan, lambda: plan.lars_norms(torch.float32, nrm), args.iters), "libgsync")
-    upd = timeit_plan(plan, lars_step, args.iters, kind=L.GS_OP_LARS, per=2)
-    _LAST.pop("fn")  # the update is not launched alone: no batched figure for it
-    rec("lars_update", 20 * n, *upd, "libgsync")
-    both = timeit(lars_step, args.iters)  # one event pair around the two launches
-    rec("lars_step", 28 * n, *both, "libgsync")
+    if want("lars"):
+        rec("lars_norms", 8 * n, *timeit_plan(plan, lambda: plan.lars_norms(torch.float32, nrm), args.iters), "libgsync")
+        upd = timeit_plan(plan, lars_step, args.iters, kind=L.GS_OP_LARS, per=2)
+        _LAST.pop("fn")  # the update is not launched alone: no batched figure for it
+        rec("lars_update", 20 * n, *upd, "libgsync")
+        both = timeit(lars_step, args.iters)  # one event pair around the two launches
+        rec("lars_step", 28 * n, *both, "libgsync")
     plan.set_ptrs(2, ms)
     plan.set_ptrs(3, vs)
-    rec("adam", 28 * n, *timeit_plan(plan, lambda: plan.adam(torch.float32, 1e-6, 0.9, 0.999, 1e-8, 0.0, False, False, -1e-6, 0.5),
-                                     args.iters), "libgsync")
-    if not args.skip_torch:
+    if want("adam"):
+        rec("adam", 28 * n, *timeit_plan(
+            plan, lambda: plan.adam(torch.float32, 1e-6, 0.9, 0.999, 1e-8, 0.0, False, False, -1e-6, 0.5), args.iters),
+            "libgsync")
+    # LAMB (FusedLAMB's two launches on the same four streams; 1-D tensors unadapted, as its
+    # default): the moments pass alone, the update as it runs in a step (right behind the
+    # moments pass that wrote m, v and read p), and the pair
+    lamb_hp = (1e-6, 0.01, 0.1, 0.0316)  # eps, wd, bc1, bc2s
+
+    def lamb_moments():
+        plan.lamb_moments(torch.float32, 0.9, 0.999, *lamb_hp, nrm)
+
+    def lamb_step():
+        lamb_moments()
+        plan.lamb(1e-6, *lamb_hp, nrm)
+
+    if want("lamb"):
+        rec("lamb_moments", 24 * n, *timeit_plan(plan, lamb_moments, args.iters), "libgsync")
+        upd = timeit_plan(plan, lamb_step, args.iters, kind=L.GS_OP_LAMB, per=2)
+        _LAST.pop("fn")  # the update is not launched alone: no batched figure for it
+        rec("lamb_update", 16 * n, *upd, "libgsync")
+        both = timeit(lamb_step, args.iters)  # one event pair around the two launches
+        rec("lamb_step", 40 * n, *both, "libgsync")
+    if not args.skip_torch and want("lamb"):
+        # a LAMB step of the same arithmetic as torch foreach ops, everything on the device
+        bp, bm, bv = [p.clone() for p in params], [x.clone() for x in ms], [x.clone() for x in vs]
+        b_adapt = torch.tensor([len(s) > 1 for s in shapes], device=dev)
+        b_wds = (b_adapt * 0.01).unbind()
+
+        def t_lamb():
+            torch._foreach_lerp_(bm, grads, 0.1)
+            torch._foreach_mul_(bv, 0.999)
+            torch._foreach_addcmul_(bv, grads, grads, value=0.001)
+            den = torch._foreach_sqrt(bv)
+            torch._foreach_div_(den, 0.0316)
+            torch._foreach_add_(den, 1e-6)
+            u = torch._foreach_div(bm, 0.1)
+            torch._foreach_div_(u, den)
+            torch._foreach_add_(u, torch._foreach_mul(bp, b_wds))
+            wn, un = torch.stack(torch._foreach_norm(bp)), torch.stack(torch._foreach_norm(u))
+            ratio = torch.where(b_adapt & (wn > 0) & (un > 0), wn / un, 1.0)
+            torch._foreach_add_(bp, torch._foreach_mul(u, (ratio * -1e-6).unbind()))
+
+        rec("lamb_step", 40 * n, *timeit(t_lamb, args.iters), "torch foreach composition")
+    if not args.skip_torch and (not only or want("pack", "unpack_f32", "sqnorm", "lars", "sgd", "adam")):
         inv = 1.0 / 8
 
         def t_pack():

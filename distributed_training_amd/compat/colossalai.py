@@ -14,7 +14,7 @@ TorchDDPPlugin -> libgsync DistributedDataParallel (+ fp16 autocast and the
 libgsync GradScaler for mixed_precision='fp16', the run.sh default).
 LowLevelZeroPlugin -> libgsync ZeRO (stage 1 default, fp16 params, fp32
 master, dynamic loss scale).  HybridAdam -> libgsync FusedAdam (AdamW mode,
-Colossal's default).  ColossalAI is not installed here: its numerics are
+Colossal's default); Lamb / FusedLAMB -> libgsync FusedLAMB (TorchDDPPlugin only).  ColossalAI is not installed here: its numerics are
 restated from the published algorithm, parity unpinned.
 """
 from __future__ import annotations
@@ -30,6 +30,7 @@ import torch.nn as nn
 from ..amp import GradScaler
 from ..ddp import DistributedDataParallel
 from ..optim import FusedAdam
+from ..optim import FusedLAMB as _FusedLAMB
 from ..zero import DynamicLossScaler, ZeroDataParallel
 
 
@@ -86,6 +87,47 @@ class HybridAdam(FusedAdam):
         super().__init__(model_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=adamw_mode,
                          capturable=bool(kw.pop("capturable", False)))
         self.colossal_kwargs = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw_mode=adamw_mode)
+
+
+class Lamb(_FusedLAMB):
+    """``colossalai.nn.optimizer.Lamb``'s signature on libgsync's FusedLAMB: every
+    tensor adapted, no bias correction (as that class); ``adam=True`` turns the trust
+    ratio off.  The arithmetic is libgsync's LAMB contract (``include/gsync.h``);
+    Colossal's clamp of the weight norm to [0, 10] is not restated."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, adam=False, **kw):
+        params = list(params)
+        if params and not isinstance(params[0], dict):
+            params = [{"params": params}]
+        for g in params:
+            g.setdefault("adapt", not adam)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bias_correction=False,
+                         capturable=bool(kw.pop("capturable", False)))
+
+
+class FusedLAMB(_FusedLAMB):
+    """``colossalai.nn.optimizer.FusedLAMB``'s (apex's) signature on libgsync's
+    FusedLAMB: decoupled weight decay (``adam_w_mode=True``), ``max_grad_norm`` as
+    the global pre-normalisation of the grads; the tensors with ``ndim > 1`` are
+    adapted, ``use_nvlamb=True`` adapts all."""
+
+    def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01,
+                 amsgrad=False, adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0,
+                 use_nvlamb=False, **kw):
+        if amsgrad:
+            raise NotImplementedError("FusedLAMB: amsgrad is not provided")
+        if not adam_w_mode or not grad_averaging:
+            raise NotImplementedError("FusedLAMB: adam_w_mode=False / grad_averaging=False are not provided")
+        params = list(params)
+        if use_nvlamb:
+            if params and not isinstance(params[0], dict):
+                params = [{"params": params}]
+            for g in params:
+                g.setdefault("adapt", True)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                         bias_correction=bias_correction, max_grad_norm=max_grad_norm or None,
+                         capturable=bool(kw.pop("capturable", False)))
+        self.set_grad_none = set_grad_none
 
 
 class _DPPluginBase:
@@ -225,6 +267,10 @@ class LowLevelZeroPlugin(_DPPluginBase):
 
     def configure(self, model, optimizer, mixed_precision):
         dtype = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}[self.precision]
+        if isinstance(optimizer, _FusedLAMB):
+            raise NotImplementedError(
+                "LAMB under ZeRO: a shard's norm would span ranks (LAMB's per-tensor trust ratio needs "
+                "whole tensors); use TorchDDPPlugin")
         model = model.to(get_current_device()).to(dtype)
         hp = getattr(optimizer, "colossal_kwargs", None) or dict(
             lr=optimizer.param_groups[0]["lr"], betas=optimizer.param_groups[0].get("betas", (0.9, 0.999)),

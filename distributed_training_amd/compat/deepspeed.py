@@ -8,7 +8,7 @@ Covered surface:
   engine.backward(loss) / engine.step() / engine.local_rank :154-155, :241
   engine.bfloat16_enabled() / fp16_enabled()                :245-248
   deepspeed.accelerator.get_accelerator().device_name(i)    :240
-  the config keys of :172-220 (train_batch_size, optimizer Adam/AdamW/SGD,
+  the config keys of :172-220 (train_batch_size, optimizer Adam/AdamW/SGD/Lamb,
   WarmupLR, gradient_clipping, bf16 / fp16 (dynamic loss scale), zero_optimization
   stage 0-2 with reduce_bucket_size / allgather_bucket_size / overlap_comm).
   engine.save_checkpoint / load_checkpoint (DeepSpeed's directory layout) and
@@ -33,7 +33,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from ..ddp import DistributedDataParallel
-from ..optim import FusedAdam, FusedSGD
+from ..optim import FusedAdam, FusedLAMB, FusedSGD
 from ..zero import DynamicLossScaler, ZeroDataParallel, warmup_lr
 
 
@@ -201,6 +201,8 @@ class DeepSpeedEngine(nn.Module):
             kind = "adamw" if adamw else "adam"
         elif otype == "sgd":
             kind = "sgd"
+        elif otype in ("lamb", "fusedlamb"):
+            kind = "lamb"
         else:
             raise NotImplementedError(f"optimizer type {opt_cfg.get('type')} is not on the gradient-sync path")
         betas = tuple(p.get("betas", (0.9, 0.999)))
@@ -209,6 +211,10 @@ class DeepSpeedEngine(nn.Module):
         use_zero = stage in (1, 2) or dtype != torch.float32
         self._ddp = None
         self._zero = None
+        if kind == "lamb" and use_zero:
+            raise NotImplementedError(
+                "optimizer type Lamb under ZeRO or 16-bit training: a shard's norm would span ranks "
+                "(LAMB's per-tensor trust ratio needs whole tensors); use stage 0 in fp32")
         if use_zero:
             self._zero = ZeroDataParallel(
                 self.module, stage=max(1, stage), optimizer=kind, lr=lr, betas=betas, eps=eps, weight_decay=wd,
@@ -226,6 +232,16 @@ class DeepSpeedEngine(nn.Module):
             if kind == "sgd":
                 self.optimizer = FusedSGD(self.module.parameters(), lr=lr, momentum=p.get("momentum", 0.0),
                                           weight_decay=wd, max_grad_norm=self.clip or None)
+            elif kind == "lamb":
+                # DeepSpeed's FusedLamb: its names and defaults (max_coeff / min_coeff clamp the
+                # trust ratio), every tensor adapted, gradient_clipping as the pre-normalisation
+                if p.get("amsgrad", False) or p.get("eps_inside_sqrt", False):
+                    raise NotImplementedError("Lamb: amsgrad / eps_inside_sqrt are not provided")
+                params = [{"params": list(self.module.parameters()), "adapt": True}]
+                self.optimizer = FusedLAMB(params, lr=lr, betas=betas, eps=eps, weight_decay=wd,
+                                           bias_correction=p.get("bias_correction", True),
+                                           min_trust=p.get("min_coeff", 0.01), max_trust=p.get("max_coeff", 10.0),
+                                           max_grad_norm=self.clip or p.get("max_grad_norm", 0.0) or None)
             else:
                 self.optimizer = FusedAdam(self.module.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=wd,
                                            adamw=kind == "adamw", max_grad_norm=self.clip or None)

@@ -165,6 +165,45 @@ GS_HD_INL void lars_coef(const LarsHyper& h, float sp, float sg, int adapt, bool
   }
   *slr = h.lr * ratio;
 }
+// LAMB (gs_lamb_moments / gs_lamb_step): w1 = float(1-b1), w2 = float(1-b2), bc2s = float(sqrt(1-b2^step));
+// lo, hi = the trust-ratio clamp (0, +inf: none)
+struct LambHyper {
+  float b1, b2, w1, w2, bc1, bc2s, eps, wd, lr, lo, hi;
+};
+// LAMB's update direction of one element from (p, m', v') (include/gsync.h, gs_lamb_moments):
+// the moments pass sums its square and the update pass recomputes it from the stored
+// moments, so both compile this one text (as does the host backend) and the recomputed
+// value is the summed one bit for bit.  Every operation rounded once, no fma.
+GS_HD_INL float lamb_update(const LambHyper& h, float p, float m, float v, float wd_t) {
+  float u = (m / h.bc1) / (sqrtf(v) / h.bc2s + h.eps);
+  if (wd_t != 0.f) u = u + wd_t * p;
+  return u;
+}
+// ... and the moments themselves: g is already multiplied
+GS_HD_INL void lamb_moments(const LambHyper& h, float g, float* m, float* v) {
+  *m = *m * h.b1 + h.w1 * g;
+  *v = *v * h.b2 + (h.w2 * g) * g;
+}
+// The per-tensor learning rate of LAMB from the tensor's Σp², Σu² (gs_lamb_step)
+GS_HD_INL float lamb_coef(const LambHyper& h, float sp, float su, int adapt) {
+  float ratio = 1.f;
+  if (adapt != 0) {
+    const float wn = sqrtf(sp), un = sqrtf(su);
+    if (wn > 0.f && un > 0.f) {
+      ratio = wn / un;
+      if (ratio < h.lo) ratio = h.lo;
+      if (ratio > h.hi) ratio = h.hi;
+    }
+  }
+  return h.lr * ratio;
+}
+inline LambHyper make_lamb(double b1, double b2, double bc1, double bc2s, double eps, double wd, double lr, double lo,
+                           double hi) {
+  return LambHyper{static_cast<float>(b1), static_cast<float>(b2), static_cast<float>(1.0 - b1),
+                   static_cast<float>(1.0 - b2), static_cast<float>(bc1), static_cast<float>(bc2s),
+                   static_cast<float>(eps), static_cast<float>(wd), static_cast<float>(lr),
+                   static_cast<float>(lo), static_cast<float>(hi)};
+}
 // Gradient-norm clip folded into an update launch (gs_plan_set_clip): the
 // update's workgroups form the coefficient themselves, so no coefficient
 // launch (and, with the plan's own group sums, no combine launch) sits between
@@ -247,7 +286,7 @@ struct gs_plan {
   bool grads_read = false;      // a Σg² pass read slot 1 since the last update (load policy)
   int read_hint = 0;            // Σg² loads: 0 the size rule, 1 non-temporal, 2 cached (gs_plan_set_read_hint)
   float h_red = 0.f;            // host plans: the Σg² of gs_sqnorm_partial
-  // LARS (gs_lars_norms / gs_lars_step): the per-tensor adaptation flags (empty = all 1)
+  // LARS and LAMB (gs_lars_norms / gs_lars_step, gs_lamb_moments / gs_lamb_step): the per-tensor adaptation flags (empty = all 1)
   // and, on HIP plans, the segmented reduction's scratch, allocated on first use:
   // d_lars = chunk slot bases | per-tensor [first slot, count] | adapt | partial slots
   std::vector<int32_t> adapt;
@@ -304,6 +343,17 @@ GS_HD inline void adam_hyper_update(double* step, const double* lr, double beta1
   hyper[1] = static_cast<float>(sqrt(bc2));
   hyper[2] = static_cast<float>(1.0 - lr[0] * wd);
 }
+// LAMB's counterpart (gs_lamb_hyper): hyper = [lr, 1 - b1^step, sqrt(1 - b2^step)] rounded
+// to fp32 (both corrections 1 when bias correction is off)
+GS_HD inline void lamb_hyper_update(double* step, const double* lr, double beta1, double beta2,
+                                    int bias_correction, const float* found_inf, float* hyper) {
+  double s = step[0];
+  if (found_inf == nullptr || found_inf[0] == 0.f) s += 1.0;
+  step[0] = s;
+  hyper[0] = static_cast<float>(lr[0]);
+  hyper[1] = bias_correction ? static_cast<float>(1.0 - pow(beta1, s)) : 1.f;
+  hyper[2] = bias_correction ? static_cast<float>(sqrt(1.0 - pow(beta2, s))) : 1.f;
+}
 int hip_adam_hyper(double* step, const double* lr, double beta1, double beta2, double wd,
                    const float* found_inf, float* hyper, void* stream);
 
@@ -356,6 +406,11 @@ int hip_lars_set_adapt(gs_plan* p);  // upload p->adapt (allocates the LARS scra
 int hip_lars_norms(gs_plan* p, int gdt, float* norms, void* stream);
 int hip_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gs, const float* fi,
              void* stream);
+int hip_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, const float* gs, const float* fi,
+                     void* stream);
+int hip_lamb(gs_plan* p, const LambHyper& h, const float* norms, const float* fi, void* stream);
+int hip_lamb_hyper(double* step, const double* lr, double beta1, double beta2, int bias_correction,
+                   const float* found_inf, float* hyper, void* stream);
 int hip_device_count();
 int hip_memset_async(void* dst, int value, size_t bytes, void* stream);
 int hip_stream_wait(void* waiter, void* signaler);
@@ -377,6 +432,8 @@ int host_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gs,
               const ClipArgs* clip);
 int host_lars_norms(gs_plan* p, int gdt, float* norms);
 int host_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gs, const float* fi);
+int host_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, const float* gs, const float* fi);
+int host_lamb(gs_plan* p, const LambHyper& h, const float* norms, const float* fi);
 // the clip coefficient of ClipArgs on the host (groups == 0: *sq is final)
 float host_clip_factor(const ClipArgs& c, const float* gs);
 // the device's 64-lane DPP fold (gs_kernels.hip wave_reduce) restated on the

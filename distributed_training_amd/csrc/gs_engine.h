@@ -1097,6 +1097,49 @@ struct LarsOp {
   }
 };
 
+// LAMB's second pass (gs_lamb_step): slots 0 = p, 2 = exp_avg, 3 = exp_avg_sq (all f32), as
+// the moments pass left them.  Every lane forms its tensor's slr from the tensor's Σp², Σu²
+// (lamb_coef) and takes its wd_t once, in load; u is recomputed by the text the moments
+// pass summed (lamb_update).  No fma: the contract rounds every operation once.
+#ifndef GS_G_LAMB
+#define GS_G_LAMB 4
+#endif
+template <int N>
+struct LambOp {
+  static constexpr int kN = N;
+  static constexpr int kG = GS_G_LAMB;
+  static constexpr int kRed = 0;
+  static constexpr int kRedGrid = kGridLimit;
+  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
+  static constexpr int kKind = GS_OP_LAMB;
+  float* partials = nullptr;
+  LambHyper h;
+  const float* norms;            // [2n]: Σp², Σu² per tensor
+  const int32_t* adapt;          // [n]
+  const float* found_inf;
+  const float* hyper = nullptr;  // [lr, bc1, bc2s] in device memory (gs_plan_set_hyper_source)
+  struct Frag { float p[N], m[N], v[N], slr, wd; };
+  __device__ int phys(int k) const { return k; }
+  __device__ bool active() const { return found_inf == nullptr || *found_inf == 0.f; }
+  __device__ bool fast_ok(const TV& tv) const { return tv.vec(0) && tv.vec(2) && tv.vec(3); }
+  template <bool F>
+  __device__ void load(const TV& tv, int64_t e0, uint32_t lo, Frag& f) const {
+    ld<GS_F32, N, F>(tv.ptr[0], e0, lo, tv.numel, tv.vec(0), f.p);
+    ld<GS_F32, N, F>(tv.ptr[2], e0, lo, tv.numel, tv.vec(2), f.m);
+    ld<GS_F32, N, F>(tv.ptr[3], e0, lo, tv.numel, tv.vec(3), f.v);
+    const int t = tv.pad;
+    const int ad = adapt[t];
+    f.slr = lamb_coef(h, norms[2 * t], norms[2 * t + 1], ad);
+    f.wd = ad != 0 ? h.wd : 0.f;
+  }
+  template <bool F>
+  __device__ void apply(const TV& tv, int64_t e0, uint32_t lo, Frag& f, float&) const {
+#pragma unroll
+    for (int i = 0; i < N; ++i) f.p[i] = f.p[i] - f.slr * lamb_update(h, f.p[i], f.m[i], f.v[i], f.wd);
+    st<GS_F32, N, F>(tv.ptr[0], e0, lo, tv.numel, tv.vec(0), f.p);
+  }
+};
+
 // Adam/AdamW: slots 0 = p, 1 = g, 2 = exp_avg, 3 = exp_avg_sq, 4 = low-precision copy
 template <int N, int GD, int LD, bool NTG = true>
 struct AdamOp {
@@ -1228,6 +1271,14 @@ __device__ __forceinline__ void load_hyper(LarsOp<N, GD, NTG>& op) {
   if (op.hyper) op.h.lr = op.hyper[0];
   op.use_gs = op.gscale != nullptr;
   op.gsv = op.gscale ? *op.gscale : 1.f;
+}
+template <int N>
+__device__ __forceinline__ void load_hyper(LambOp<N>& op) {
+  if (op.hyper) {
+    op.h.lr = op.hyper[0];
+    op.h.bc1 = op.hyper[1];
+    op.h.bc2s = op.hyper[2];
+  }
 }
 template <int N, int GD, int LD, bool NTG>
 __device__ __forceinline__ void load_hyper(AdamOp<N, GD, LD, NTG>& op) {

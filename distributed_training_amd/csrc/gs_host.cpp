@@ -439,6 +439,67 @@ int host_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const
   return GS_OK;
 }
 
+// LAMB on the host (include/gsync.h, gs_lamb_moments / gs_lamb_step): the device kernels'
+// contract and the same text of the update (lamb_moments / lamb_update / lamb_coef,
+// gs_common.h).  Sums in element order, 1 Ki-element blocks folded front to back, as
+// host_lars_norms.
+int host_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, const float* gsc, const float* fi) {
+  constexpr int64_t kBlk = 1024;
+  GS_TRY_RET(check_float(gdt));
+  if (fi && fi[0] != 0.f) return GS_OK;
+  const bool has_m = gsc != nullptr;
+  const float mul = gsc ? gsc[0] : 1.f;
+  GS_HOST_FLOAT(gdt, GD, {
+    for (int t = 0; t < p->n; ++t) {
+      const float* pp = static_cast<const float*>(slot(p, 0, t));
+      const void* gp = slot(p, 1, t);
+      float* mp = static_cast<float*>(slot(p, 2, t));
+      float* vp = static_cast<float*>(slot(p, 3, t));
+      const float wd_t = (p->adapt.empty() || p->adapt[t] != 0) ? h.wd : 0.f;
+      float sp = 0.f, su = 0.f;
+      for (int64_t i0 = 0; i0 < p->numel[t]; i0 += kBlk) {
+        const int64_t i1 = std::min(p->numel[t], i0 + kBlk);
+        float bp = 0.f, bu = 0.f;
+        for (int64_t i = i0; i < i1; ++i) {
+          float g = ldT<GD>(gp, i);
+          if (has_m) g = g * mul;
+          float m = mp[i], v = vp[i];
+          lamb_moments(h, g, &m, &v);
+          const float x = pp[i];
+          const float u = lamb_update(h, x, m, v, wd_t);
+          mp[i] = m;
+          vp[i] = v;
+          bp = bp + x * x;
+          bu = bu + u * u;
+        }
+        sp = sp + bp;
+        su = su + bu;
+      }
+      norms[2 * t] = sp;
+      norms[2 * t + 1] = su;
+    }
+  });
+  return GS_OK;
+}
+
+int host_lamb(gs_plan* p, const LambHyper& h, const float* norms, const float* fi) {
+  if (fi && fi[0] != 0.f) return GS_OK;
+  std::vector<float> slr(p->n), wdt(p->n);
+  for (int t = 0; t < p->n; ++t) {
+    const int ad = p->adapt.empty() ? 1 : p->adapt[t];
+    slr[t] = lamb_coef(h, norms[2 * t], norms[2 * t + 1], ad);
+    wdt[t] = ad != 0 ? h.wd : 0.f;
+  }
+  for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
+    float* pp = static_cast<float*>(slot(p, 0, t));
+    const float* mp = static_cast<const float*>(slot(p, 2, t));
+    const float* vp = static_cast<const float*>(slot(p, 3, t));
+    const float lr_t = slr[t], wd_t = wdt[t];
+    for (int64_t i = i0; i < i1; ++i) pp[i] = pp[i] - lr_t * lamb_update(h, pp[i], mp[i], vp[i], wd_t);
+  });
+  return GS_OK;
+}
+
 }  // namespace gs
 
 extern "C" int gs_set_host_threads(int n) {

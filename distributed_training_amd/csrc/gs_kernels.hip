@@ -427,6 +427,19 @@ int hip_adam_hyper(double* step, const double* lr, double beta1, double beta2, d
   return GS_OK;
 }
 
+__global__ void lamb_hyper_kernel(double* step, const double* lr, double beta1, double beta2, int bias_correction,
+                                  const float* found_inf, float* hyper) {
+  if (threadIdx.x == 0) lamb_hyper_update(step, lr, beta1, beta2, bias_correction, found_inf, hyper);
+}
+
+int hip_lamb_hyper(double* step, const double* lr, double beta1, double beta2, int bias_correction,
+                   const float* found_inf, float* hyper, void* stream) {
+  hipLaunchKernelGGL(lamb_hyper_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), step, lr,
+                     beta1, beta2, bias_correction, found_inf, hyper);
+  HIP_RET(hipGetLastError());
+  return GS_OK;
+}
+
 template <bool NT>
 static int clip_scale_nt(gs_plan* p, int slot, int dt, const ClipArgs& clip, void* stream) {
   GS_DISPATCH_FLOAT(dt, DT, {

@@ -584,6 +584,72 @@ int gs_lars_step(gs_plan* p, int grad_dtype, double lr, double momentum, double 
   return hip_lars(p, grad_dtype, h, norms, grad_scale_dev, found_inf_dev, stream);
 }
 
+static int lamb_args_ok(const gs_plan* p, double eps, double wd, double bc1, double bc2s, const char* who) {
+  if (!(eps >= 0 && wd >= 0))
+    return fail(GS_EINVAL, std::string(who) + ": eps and weight_decay must be >= 0");
+  if (!p->hyper && !(bc1 > 0 && bc2s > 0))
+    return fail(GS_EINVAL, std::string(who) + ": bc1 and bc2_sqrt must be > 0");
+  if (p->clip_on)
+    return fail(GS_ESTATE, std::string(who) + ": a gradient-norm clip is set on the plan (gs_plan_set_clip); "
+                           "pass LAMB's pre-normalisation as the grad multiplier");
+  return GS_OK;
+}
+
+int gs_lamb_moments(gs_plan* p, int grad_dtype, double beta1, double beta2, double eps, double weight_decay,
+                    double bc1, double bc2_sqrt, float* norms_out, const float* grad_scale_dev,
+                    const float* found_inf_dev, void* stream) {
+  GsRange range("gs_lamb_moments");
+  PLAN_OK(p);
+  GS_CHECK_ARG(is_float_dtype(grad_dtype), "gs_lamb_moments: grad dtype must be f32, bf16 or f16");
+  GS_CHECK_ARG(p->n == 0 || norms_out != nullptr, "gs_lamb_moments: NULL output");
+  GS_CHECK_ARG(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1, "gs_lamb_moments: betas must be in [0, 1)");
+  GS_TRY_RET(lamb_args_ok(p, eps, weight_decay, bc1, bc2_sqrt, "gs_lamb_moments"));
+  GS_TRY_RET(lars_slots_bound(p, 4, "gs_lamb_moments"));
+  LambHyper h = make_lamb(beta1, beta2, bc1, bc2_sqrt, eps, weight_decay, 0.0, 0.0, 0.0);
+  if (p->kind == GS_DEV_HOST) {
+    if (p->hyper) {
+      h.bc1 = p->hyper[1];
+      h.bc2s = p->hyper[2];
+    }
+    return host_lamb_moments(p, grad_dtype, h, norms_out, grad_scale_dev, found_inf_dev);
+  }
+  return hip_lamb_moments(p, grad_dtype, h, norms_out, grad_scale_dev, found_inf_dev, stream);
+}
+
+int gs_lamb_step(gs_plan* p, double lr, double eps, double weight_decay, double bc1, double bc2_sqrt,
+                 double min_ratio, double max_ratio, const float* norms, const float* found_inf_dev, void* stream) {
+  GsRange range("gs_lamb_step");
+  PLAN_OK(p);
+  GS_CHECK_ARG(p->n == 0 || norms != nullptr, "gs_lamb_step: NULL norms");
+  GS_CHECK_ARG(min_ratio >= 0 && max_ratio >= min_ratio, "gs_lamb_step: 0 <= min_ratio <= max_ratio");
+  GS_TRY_RET(lamb_args_ok(p, eps, weight_decay, bc1, bc2_sqrt, "gs_lamb_step"));
+  for (int t = 0; t < p->n; ++t)
+    for (int s : {0, 2, 3})
+      if (p->numel[t] > 0 && p->h_ptrs[static_cast<size_t>(s) * p->n + t] == nullptr)
+        return fail(GS_EINVAL, "gs_lamb_step: slot " + std::to_string(s) + " of tensor " + std::to_string(t) +
+                                   " is not bound");
+  LambHyper h = make_lamb(0.0, 0.0, bc1, bc2_sqrt, eps, weight_decay, lr, min_ratio, max_ratio);
+  if (p->kind == GS_DEV_HOST) {
+    if (p->hyper) {
+      h.lr = p->hyper[0];
+      h.bc1 = p->hyper[1];
+      h.bc2s = p->hyper[2];
+    }
+    return host_lamb(p, h, norms, found_inf_dev);
+  }
+  return hip_lamb(p, h, norms, found_inf_dev, stream);
+}
+
+int gs_lamb_hyper(int device_kind, double* step, const double* lr, double beta1, double beta2, int bias_correction,
+                  const float* found_inf, float* hyper, void* stream) {
+  GS_CHECK_ARG(step && lr && hyper, "gs_lamb_hyper: NULL argument");
+  if (device_kind == GS_DEV_HOST) {
+    lamb_hyper_update(step, lr, beta1, beta2, bias_correction, found_inf, hyper);
+    return GS_OK;
+  }
+  return hip_lamb_hyper(step, lr, beta1, beta2, bias_correction, found_inf, hyper, stream);
+}
+
 int gs_plan_set_hyper_source(gs_plan* p, const float* hyper) {
   PLAN_OK(p);
   p->hyper = hyper;

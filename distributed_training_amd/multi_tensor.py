@@ -98,7 +98,7 @@ class TensorListPlan:
     def set_hyper_source(self, hyper: torch.Tensor | None):
         """Later sgd()/adam() launches read their step-varying hyper-parameters
         from ``hyper`` (fp32, on the plan's device) when they run — SGD [lr];
-        Adam [step_size, bias_correction2_sqrt, 1 - lr*wd] — instead of their
+        Adam [step_size, bias_correction2_sqrt, 1 - lr*wd]; LAMB [lr, bc1, bc2s] — instead of their
         arguments (gs_plan_set_hyper_source).  The plan keeps a reference."""
         if hyper is not None:
             if hyper.dtype != torch.float32 or not hyper.is_contiguous() or hyper.numel() < 3:
@@ -271,7 +271,7 @@ class TensorListPlan:
     def _norms_ok(self, norms: torch.Tensor):
         if norms.dtype != torch.float32 or not norms.is_contiguous() or norms.numel() < 2 * self.n or \
                 not self._where_plan(norms):
-            raise ValueError(f"LARS norms: contiguous fp32[>= {2 * self.n}] where the plan runs")
+            raise ValueError(f"per-tensor norms: contiguous fp32[>= {2 * self.n}] where the plan runs")
 
     def lars_norms(self, grad_dtype, out: torch.Tensor, stream=None):
         """out[2t] = Σp², out[2t+1] = Σg² of tensor t (slot 0 = params, slot 1 =
@@ -292,6 +292,37 @@ class TensorListPlan:
                 None if grad_scale is None else grad_scale.data_ptr(),
                 None if found_inf is None else found_inf.data_ptr(), self._stream(stream)),
             "gs_lars_step",
+        )
+
+    # ------------------------------------------------------------------ LAMB
+    def lamb_moments(self, grad_dtype, beta1, beta2, eps, wd, bc1, bc2s, norms: torch.Tensor,
+                     grad_scale=None, found_inf=None, stream=None):
+        """LAMB's first pass on slots 0 = p, 1 = g, 2 = exp_avg, 3 = exp_avg_sq: the
+        moments advance in place and norms[2t] = Σp², norms[2t+1] = Σu² of tensor t,
+        u the Adam update (+ wd*p on adapted tensors, :meth:`set_adapt`), in the
+        order of :meth:`lars_norms` (gs_lamb_moments)."""
+        self._norms_ok(norms)
+        L.check(
+            L.lib().gs_lamb_moments(
+                self.handle, L.gs_dtype(grad_dtype), float(beta1), float(beta2), float(eps), float(wd),
+                float(bc1), float(bc2s), norms.data_ptr(),
+                None if grad_scale is None else grad_scale.data_ptr(),
+                None if found_inf is None else found_inf.data_ptr(), self._stream(stream)),
+            "gs_lamb_moments",
+        )
+
+    def lamb(self, lr, eps, wd, bc1, bc2s, norms: torch.Tensor, min_ratio=0.0, max_ratio=float("inf"),
+             found_inf=None, stream=None):
+        """LAMB's second pass on slots 0, 2, 3 with the sums of :meth:`lamb_moments`
+        (same eps, wd, bc1, bc2s): p -= lr * clamp(‖p‖/‖u‖, min_ratio, max_ratio) * u,
+        u recomputed from the stored moments (gs_lamb_step)."""
+        self._norms_ok(norms)
+        L.check(
+            L.lib().gs_lamb_step(
+                self.handle, float(lr), float(eps), float(wd), float(bc1), float(bc2s), float(min_ratio),
+                float(max_ratio), norms.data_ptr(),
+                None if found_inf is None else found_inf.data_ptr(), self._stream(stream)),
+            "gs_lamb_step",
         )
 
     def adam(self, grad_dtype, lr, beta1, beta2, eps, weight_decay, adamw, maximize, step_size,

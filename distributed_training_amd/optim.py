@@ -12,6 +12,11 @@
   per-tensor ‖w‖², ‖g‖² of the whole list in one deterministic pass
   (8 B/param), then one update pass (20 B/param) that forms each tensor's trust
   ratio itself.
+* :class:`FusedLAMB` — layer-wise adaptive Adam (DeepSpeed's FusedLamb,
+  ColossalAI's Lamb / FusedLAMB; no torch counterpart): one pass that advances
+  the moments and publishes the per-tensor ‖w‖², ‖update‖² (24 B/param), then
+  one update pass (16 B/param) that recomputes the update and applies each
+  tensor's trust ratio.
 * :func:`clip_grad_norm_` — ``torch.nn.utils.clip_grad_norm_``
   (T:nn/utils/clip_grad.py:50-186) with a wave-level Σg² reduction and the
   clip coefficient kept on the device (no host sync).
@@ -257,6 +262,19 @@ class _FusedBase(torch.optim.Optimizer):
                     plan.set_clip(float(max_norm), 1e-6, raw, out=buf[0:3])
                     plan._clip_on = True
             return self.grad_scale  # the kernels fold it into the coefficient
+        return self._clip_scale_separate(device, all_plans)
+
+    def _clip_scale_separate(self, device, all_plans):
+        """The separate clip path: Σg² over all plans (gs_sqnorm + combine), the
+        coefficient min(1, max_norm/(‖g‖+1e-6)) (times grad_scale) by gs_clip_coef
+        into the clip buffer [Σg², coef, norm, -], returned as the grad multiplier."""
+        max_norm = self.defaults.get("max_grad_norm")
+        buf = self._clip_buf.get(device)
+        if buf is None:
+            buf = torch.zeros(4, dtype=torch.float32, device=device)
+            self._clip_buf[device] = buf
+        sq, coef, norm = buf[0:1], buf[1:2], buf[2:3]
+        self.last_grad_norm = norm
         for plan, _ in all_plans:
             if getattr(plan, "_clip_on", False):
                 plan.set_clip(None)
@@ -491,27 +509,10 @@ class FusedLARS(_FusedBase):
         return loss
 
 
-class FusedAdam(_FusedBase):
-    """Adam (``adamw=False``) or AdamW (``adamw=True`` / ``decoupled_weight_decay=True``)."""
+class _DeviceSteps:
+    """The Adam-family step counters (FusedAdam, FusedLAMB)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
-                 *, foreach=None, maximize=False, capturable=False, differentiable=False, fused=None,
-                 decoupled_weight_decay=False, adamw=None, max_grad_norm=None):
-        if not 0.0 <= lr:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= eps:
-            raise ValueError(f"Invalid epsilon value: {eps}")
-        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid beta parameters: {betas}")
-        if amsgrad:
-            raise NotImplementedError("FusedAdam: amsgrad is not on the reference path")
-        if differentiable:
-            raise ValueError("FusedAdam does not support differentiable=True")
-        adamw = bool(decoupled_weight_decay if adamw is None else adamw)
-        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
-                        foreach=foreach, maximize=maximize, capturable=bool(capturable), differentiable=False,
-                        fused=fused, decoupled_weight_decay=adamw, max_grad_norm=max_grad_norm)
-        super().__init__(params, defaults)
+    _name = "FusedAdam"
 
     # ---- device step counters (capturable / AMP): one fp64 counter per cohort of
     # parameters that have advanced together so far.  torch keeps one step per
@@ -532,7 +533,7 @@ class FusedAdam(_FusedBase):
             if t is not None and id(t) in cohorts:
                 continue
             if _capturing():
-                raise RuntimeError("FusedAdam: state must exist before capture (take an eager step first)")
+                raise RuntimeError(f"{self._name}: state must exist before capture (take an eager step first)")
             v = 0.0 if t is None else float(t)
             c = by_value.get(v)
             if c is None:
@@ -547,7 +548,7 @@ class FusedAdam(_FusedBase):
         """Members `ps` (with grads) leave cohort `c` (some of whose members have
         none this step) for a new one starting at the same count."""
         if _capturing():
-            raise RuntimeError("FusedAdam: the set of parameters with grads changed inside a capture")
+            raise RuntimeError(f"{self._name}: the set of parameters with grads changed inside a capture")
         n = {"step": c["step"].clone(), "hyper": torch.zeros_like(c["hyper"]), "members": {id(p) for p in ps}}
         c["members"] -= n["members"]
         h["cohorts"][id(n["step"])] = n
@@ -570,6 +571,29 @@ class FusedAdam(_FusedBase):
                 dev = t.device if self.capturable else torch.device("cpu")
                 sd["state"][k] = dict(st, step=torch.tensor(v, dtype=torch.float32, device=dev))
         return sd
+
+
+class FusedAdam(_DeviceSteps, _FusedBase):
+    """Adam (``adamw=False``) or AdamW (``adamw=True`` / ``decoupled_weight_decay=True``)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
+                 *, foreach=None, maximize=False, capturable=False, differentiable=False, fused=None,
+                 decoupled_weight_decay=False, adamw=None, max_grad_norm=None):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if amsgrad:
+            raise NotImplementedError("FusedAdam: amsgrad is not on the reference path")
+        if differentiable:
+            raise ValueError("FusedAdam does not support differentiable=True")
+        adamw = bool(decoupled_weight_decay if adamw is None else adamw)
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
+                        foreach=foreach, maximize=maximize, capturable=bool(capturable), differentiable=False,
+                        fused=fused, decoupled_weight_decay=adamw, max_grad_norm=max_grad_norm)
+        super().__init__(params, defaults)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -682,6 +706,184 @@ class FusedAdamW(FusedAdam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
         kw.pop("decoupled_weight_decay", None)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=True, **kw)
+
+
+class FusedLAMB(_DeviceSteps, _FusedBase):
+    """LAMB (You et al. 2019; DeepSpeed's ``FusedLamb``, ColossalAI's ``Lamb`` /
+    ``FusedLAMB``, apex's ``FusedLAMB``): Adam whose update is multiplied, per
+    tensor, by the trust ratio ``‖w‖ / ‖update‖``.
+
+    Two kernels per (param group, grad dtype): ``gs_lamb_moments`` advances
+    ``exp_avg`` / ``exp_avg_sq`` and publishes the per-tensor Σp², Σu² in one
+    deterministic pass (24 B/param), then ``gs_lamb_step`` recomputes the update
+    from the stored moments and writes p (16 B/param) — instead of a
+    ``torch.norm`` pair per parameter plus the foreach moments and update.  There
+    is no torch LAMB to match: the arithmetic is the contract in
+    ``include/gsync.h`` (fp32, every operation rounded once)::
+
+        g = g (* grad multiplier); m = m*b1 + (1-b1)*g; v = v*b2 + ((1-b2)*g)*g
+        u = (m/bc1) / (sqrt(v)/sqrt(bc2) + eps) (+ wd*p on adapted tensors)
+        adapted:   ratio = clamp(‖p‖/‖u‖, min_trust, max_trust) if ‖p‖ > 0 and ‖u‖ > 0 else 1
+        unadapted: ratio = 1 (plain Adam, no decay)
+        p = p - (lr*ratio)*u
+
+    The param-group key ``adapt`` works as in :class:`FusedLARS`: ``None``
+    (default) adapts the tensors with ``p.ndim > 1``, ``True`` all, ``False``
+    none.  State is ``step``, ``exp_avg``, ``exp_avg_sq`` (torch Adam's keys).
+    Parameters are fp32 and dense; grads fp32, bf16 or fp16, one plan per (group,
+    grad dtype).  ``grad_scale`` / ``found_inf`` behave as in the other fused
+    optimizers (``amp.GradScaler`` drives it unchanged).  ``max_grad_norm`` is
+    apex / DeepSpeed LAMB's global pre-normalisation: Σg² over all plans, the
+    clip coefficient on the device, passed as the grad multiplier (the separate
+    clip path; LAMB does not take the clip folded into the update).
+    ``capturable=True`` with :meth:`refresh_hyper` lets ``graphs.CapturedStep``
+    record it (take one eager step first: state and scratch must exist).
+
+    Out of scope: ZeRO shards (a tensor's norm would span ranks),
+    ``DDP._register_fused_optim``, amsgrad, low-precision parameter copies.
+    """
+
+    _name = "FusedLAMB"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, bias_correction=True,
+                 min_trust=None, max_trust=None, max_grad_norm=None, *, capturable=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        lo = 0.0 if min_trust is None else float(min_trust)
+        hi = math.inf if max_trust is None else float(max_trust)
+        if not 0.0 <= lo <= hi:
+            raise ValueError(f"Invalid trust-ratio clamp: [{min_trust}, {max_trust}]")
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                        bias_correction=bool(bias_correction), min_trust=min_trust, max_trust=max_trust,
+                        max_grad_norm=max_grad_norm, adapt=None, capturable=bool(capturable))
+        super().__init__(params, defaults)
+        self._last_norms: list = []
+
+    def kernel_ms(self) -> list:
+        """Durations (ms) of the moments passes and the updates since the last call, all plans."""
+        kinds = (L.GS_OP_LAMB_MOMENTS, L.GS_OP_LAMB)
+        return [ms for plan in self._plans.plans() if plan.kind == L.GS_DEV_HIP
+                for k, v in plan.timer_read_by_kind().items() if k in kinds for ms in v]
+
+    def sq_norms(self) -> list:
+        """[(params, norms)] per plan of the last step: ``norms`` is the fp32[2n]
+        tensor the step published, [2t] = Σp² (before the update), [2t+1] = Σu²
+        of ``params[t]`` (overwritten by the next step)."""
+        return list(self._last_norms)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        cap = self._device_state()  # device step counters: capturable or AMP (no host read of found_inf)
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            buckets: dict = {}
+            by_cohort: dict = {}
+            h = None
+            live = []
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("FusedLAMB does not support sparse gradients")
+                _check_dense(p, p.grad, "FusedLAMB", self._dense_seen)
+                if p.dtype != torch.float32:
+                    raise RuntimeError("FusedLAMB expects fp32 parameters (keep a fp32 master copy)")
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    if _capturing():
+                        raise RuntimeError("FusedLAMB: state must exist before capture (take an eager step first)")
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                live.append(p)
+            for p in live:
+                st = self.state[p]
+                if cap:
+                    if h is None:
+                        h = self._group_hyper(gi, group, p.device)
+                    if id(st["step"]) not in h.get("cohorts", {}):
+                        self._adopt_cohorts(h, group)
+                    by_cohort.setdefault(id(st["step"]), []).append(p)
+                else:
+                    st["step"] += 1
+                    lists = buckets.setdefault((p.grad.dtype, float(st["step"].item())), ([], [], [], []))
+                    for lst, x in zip(lists, (p, p.grad, st["exp_avg"], st["exp_avg_sq"])):
+                        lst.append(x)
+            for cid, ps in by_cohort.items():
+                c = h["cohorts"][cid]
+                if len(ps) < len(c["members"]):
+                    c = self._split_cohort(h, c, ps)
+                work.append((group, None, gi, (h, c)))  # advance the cohort's counter, form its hyper source
+                for p in ps:
+                    st = self.state[p]
+                    lists = buckets.setdefault((p.grad.dtype, id(c["step"])), ([], [], [], []))
+                    for lst, x in zip(lists, (p, p.grad, st["exp_avg"], st["exp_avg_sq"])):
+                        lst.append(x)
+            cohort_hyper = {id(c["step"]): c["hyper"] for c in h["cohorts"].values()} if h is not None else {}
+            for (gdt, step), (ps, gs, ms, vs) in buckets.items():
+                plan = self._plans.get(ps)
+                plan.set_ptrs(0, ps)
+                plan.set_ptrs(1, gs)
+                plan.set_ptrs(2, ms)
+                plan.set_ptrs(3, vs)
+                adapt = group.get("adapt")
+                flags = tuple((p.ndim > 1) if adapt is None else bool(adapt) for p in ps)
+                if getattr(plan, "_adapt", None) != flags:
+                    if _capturing():
+                        raise RuntimeError("FusedLAMB: take one eager step before capturing "
+                                           "(the plan's adaptation flags and scratch are set there)")
+                    plan.set_adapt(flags)
+                    plan._adapt = flags
+                    plan._lamb_norms = torch.zeros(2 * len(ps), dtype=torch.float32, device=ps[0].device)
+                if cap:
+                    hyper = cohort_hyper[step]
+                    if getattr(plan, "_hyper", None) is not hyper:
+                        plan.set_hyper_source(hyper)
+                    step = None
+                work.append((group, plan, gdt, step, ps))
+        if not work:
+            return loss
+        if cap:
+            self.refresh_hyper()
+        plans = [(w[1], w[2]) for w in work if w[1] is not None]
+        if not plans:
+            return loss
+        self._last_norms = [(w[4], w[1]._lamb_norms) for w in work if w[1] is not None]
+        scale = self.grad_scale
+        if self.defaults.get("max_grad_norm"):
+            scale = self._clip_scale_separate(plans[0][0].device, plans)
+        for group, plan, gdt, step, *_ in work:
+            beta1, beta2 = group["betas"]
+            if plan is None:  # device counters: advance the cohort's step, form its hyper source
+                h, c = step
+                L.check(L.lib().gs_lamb_hyper(
+                    L.GS_DEV_HIP if c["step"].is_cuda else L.GS_DEV_HOST, c["step"].data_ptr(), h["lr"].data_ptr(),
+                    float(beta1), float(beta2), int(group["bias_correction"]),
+                    None if self.found_inf is None else self.found_inf.data_ptr(), c["hyper"].data_ptr(),
+                    L.stream_ptr(c["step"].device) if c["step"].is_cuda else None), "gs_lamb_hyper")
+                continue
+            bc1 = bc2s = 1.0  # step is None: the kernels read lr, bc1, bc2s from the hyper source
+            if step is not None and group["bias_correction"]:
+                bc1 = 1 - beta1 ** step
+                bc2s = math.sqrt(1 - beta2 ** step)
+            lo = 0.0 if group["min_trust"] is None else group["min_trust"]
+            hi = math.inf if group["max_trust"] is None else group["max_trust"]
+            norms = plan._lamb_norms
+            plan.lamb_moments(gdt, beta1, beta2, group["eps"], group["weight_decay"], bc1, bc2s, norms,
+                              grad_scale=scale, found_inf=self.found_inf)
+            plan.lamb(group["lr"], group["eps"], group["weight_decay"], bc1, bc2s, norms, lo, hi,
+                      found_inf=self.found_inf)
+        return loss
 
 
 _NORM_PLANS: dict = {}

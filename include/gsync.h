@@ -206,6 +206,8 @@ int64_t gs_plan_task_units(gs_plan* p);
 #define GS_OP_SUM 8
 #define GS_OP_LARS_NORM 9 /* gs_lars_norms: the segmented reduction and its finishing kernel, one record */
 #define GS_OP_LARS 10
+#define GS_OP_LAMB_MOMENTS 11 /* gs_lamb_moments: the chunk pass and its fold, one record */
+#define GS_OP_LAMB 12
 int gs_plan_timer_enable(gs_plan* p, int n_slots);
 int gs_plan_timer_read(gs_plan* p, float* ms_out, int32_t* kind_out, int cap);
 /* register the per-tensor pointers of one slot (uploads on change, ordered on `stream`) */
@@ -403,6 +405,8 @@ int gs_lars_step(gs_plan* p, int grad_dtype, double lr, double momentum, double 
  *         (cleared by the caller after a step that was not skipped)
  *   Adam: hyper[0] = step_size (-lr/bc1), hyper[1] = bias_correction2_sqrt,
  *         hyper[2] = 1 - lr*wd (AdamW decay)
+ *   LARS: hyper[0] = lr
+ *   LAMB: hyper[0] = lr, hyper[1] = bc1, hyper[2] = bc2_sqrt (gs_lamb_hyper)
  * (fp32, device memory for HIP plans, host memory for host plans) when the
  * kernel runs, so a step recorded into a hipGraph follows an LR schedule and
  * Adam's bias corrections on replay; the argument values are then ignored.
@@ -416,6 +420,68 @@ int gs_plan_set_hyper_source(gs_plan* p, const float* hyper);
  * replaces: T:optim/adam.py:640-668 (capturable branch: device step, bias corrections) */
 int gs_adam_hyper(int device_kind, double* step, const double* lr, double beta1, double beta2,
                   double weight_decay, const float* found_inf, float* hyper, void* stream);
+/* LAMB (You et al. 2019, layer-wise adaptive moments; DeepSpeed's FusedLamb, ColossalAI's
+ * Lamb / FusedLAMB): Adam whose update u is multiplied, per tensor, by the trust ratio
+ * ‖w‖ / ‖u‖.  The ratio needs the norm of the Adam update, not of the gradient, so the
+ * norm pass also advances the moments: gs_lamb_moments is one pass over (p, g, m, v) that
+ * stores m', v' and publishes the per-tensor Σp², Σu² (24 B/param with fp32 grads: reads
+ * 16, writes 8), gs_lamb_step one pass over (p, m', v') that recomputes u and writes p
+ * (16 B/param).  u is recomputed, not stored: the same 40 B/param either way, and no
+ * 4 B/param scratch.  Both use the per-tensor flags of gs_plan_set_adapt and the
+ * segmented reduction of gs_lars_norms (same slot map, same summation order).
+ *
+ * Slots: 0 = p (f32), 1 = g (grad_dtype: f32, bf16 or f16), 2 = exp_avg (f32),
+ * 3 = exp_avg_sq (f32).  Arithmetic (all fp32; every multiply, add, divide and sqrt
+ * rounded once, NO fma).  Formed on the host in double, then rounded to fp32: b1, b2,
+ * w1 = 1-beta1, w2 = 1-beta2, bc1 = 1-beta1^step, bc2s = sqrt(1-beta2^step) (both 1 when
+ * bias correction is off: the caller passes them), lr, eps, wd, lo, hi (the trust-ratio
+ * clamp; 0 and +inf mean none).
+ *   per tensor t:   wd_t = adapt[t] ? wd : 0
+ *   pass 1 (gs_lamb_moments), per element (m = *grad_scale_dev if given):
+ *       g  = float(g_i);  if (m) g = g*m
+ *       m' = m_i*b1 + w1*g
+ *       v' = v_i*b2 + (w2*g)*g
+ *       u  = (m'/bc1) / (sqrt(v')/bc2s + eps);   if (wd_t != 0) u = u + wd_t*p_i
+ *       store m', v';   sp += p_i*p_i;  su += u*u       (fixed order, as gs_lars_norms)
+ *   pass 2 (gs_lamb_step), per tensor:
+ *       wn = sqrt(sp); un = sqrt(su); ratio = 1
+ *       if (adapt[t] && wn > 0 && un > 0) { ratio = wn/un; if (ratio < lo) ratio = lo; if (ratio > hi) ratio = hi; }
+ *       slr = lr*ratio
+ *   pass 2, per element:  u recomputed from (p_i, m', v') by the same expression;  p = p_i - slr*u
+ * Both passes and the host backend compile one text of u (lamb_update, gs_common.h), so
+ * the recomputed u is the one whose square was summed, bit for bit.  eps, wd, bc1 and
+ * bc2s must be the same in both calls.
+ *
+ * found_inf_dev (nullable): *found_inf != 0 and neither pass writes p, m or v; the norms
+ * vector is then unspecified.  A clip set on the plan (gs_plan_set_clip*) is GS_ESTATE:
+ * a global pre-normalisation of the grads goes in as grad_scale_dev.  With a hyper
+ * source on the plan (gs_plan_set_hyper_source) both kernels read hyper = [lr, bc1, bc2s]
+ * from it when they run, as Adam reads its own; the argument values are then ignored.
+ * Determinism: as gs_lars_norms.  Not part of LAMB here: amsgrad, low-precision parameter
+ * copies, sharded tensors (a ZeRO shard's norm would span ranks).
+ *
+ * norms_out: fp32[2n] in the plan's memory kind: [2t] = Σp², [2t+1] = Σu² of tensor t.
+ * Two launches (the chunk pass, the per-tensor fold), one timer record (GS_OP_LAMB_MOMENTS).
+ * replaces: of a Python LAMB, the foreach moments (exp_avg.lerp_ / mul_().add_(),
+ *           exp_avg_sq.mul_().addcmul_(), the addcdiv that forms the update, add(p, alpha=wd))
+ *           and the per-parameter torch.norm(p), torch.norm(update) pair */
+int gs_lamb_moments(gs_plan* p, int grad_dtype, double beta1, double beta2, double eps, double weight_decay,
+                    double bc1, double bc2_sqrt, float* norms_out, const float* grad_scale_dev,
+                    const float* found_inf_dev, void* stream);
+/* pass 2 above on slots 0, 2, 3; norms: gs_lamb_moments' output for this step.
+ * replaces: of a Python LAMB, the per-parameter trust ratio (where / clamp) and
+ *           p.add_(update, alpha=-lr*ratio) */
+int gs_lamb_step(gs_plan* p, double lr, double eps, double weight_decay, double bc1, double bc2_sqrt,
+                 double min_ratio, double max_ratio, const float* norms, const float* found_inf_dev, void* stream);
+/* LAMB hyper source update on the stream (one thread; graph-capturable), gs_adam_hyper's
+ * counterpart:
+ *   if (!found_inf || *found_inf == 0) *step += 1;
+ *   hyper = [lr, 1 - beta1^step, sqrt(1 - beta2^step)]  in double, rounded to fp32
+ *           (bias_correction == 0: [lr, 1, 1])
+ * step, lr: fp64 scalars; hyper: fp32[3] (the plan's hyper source).
+ * replaces: the host-side `state["step"] += 1` and bias corrections of a Python LAMB */
+int gs_lamb_hyper(int device_kind, double* step, const double* lr, double beta1, double beta2, int bias_correction,
+                  const float* found_inf, float* hyper, void* stream);
 
 /* ======================================================================
  * bucket assignment (greedy by size per dtype, first-bucket cap)
