@@ -116,11 +116,12 @@ def main():
 
     last_fn = _LAST
 
-    def rec(name, nbytes, ms_med, ms_avg, impl):
+    def rec(name, nbytes, ms_med, ms_avg, impl, **extra):
         gbs = nbytes / (ms_avg * 1e-3) / 1e9
         row = {"kernel": name, "impl": impl, "model": args.model, "replicas": args.replicas, "params": n,
                "tag": args.tag, "task_units": plan.task_units, "n_tasks": plan.n_tasks,
                "alg_bytes": nbytes, "median_ms": ms_med, "avg_ms": ms_avg, "GBps": gbs, "frac_of_8TBps": gbs / HBM_PEAK}
+        row.update(extra)
         if "fn" in last_fn:  # the same launches, batched between one event pair
             bms = timeit_batched(last_fn.pop("fn"), args.iters)
             bgbs = nbytes / (bms * 1e-3) / 1e9
@@ -167,6 +168,21 @@ def main():
         upd = timeit_plan(plan, lars_step, args.iters, kind=L.GS_OP_LARS, per=2)
         _LAST.pop("fn")  # the update is not launched alone: no batched figure for it
         rec("lars_update", 20 * n, *upd, "libgsync")
+        # the same update writing a bf16 copy of the new p (slot 3, gs_lars_step_lowp: ZeRO's
+        # 16-bit model), timed the same way, then the plain update once more: the two plain
+        # figures are this run's own spread (`plain_again_ms`)
+        lowp = [torch.zeros(s, device=dev, dtype=torch.bfloat16) for s in shapes]  # kept: slot 3 / 4 point at it
+        plan.set_ptrs(3, lowp)
+
+        def lars_step_lowp():
+            plan.lars_norms(torch.float32, nrm)
+            plan.lars(*lars_args, lowp_dtype=torch.bfloat16)
+
+        upd16 = timeit_plan(plan, lars_step_lowp, args.iters, kind=L.GS_OP_LARS, per=2)
+        again = timeit_plan(plan, lars_step, args.iters, kind=L.GS_OP_LARS, per=2)
+        _LAST.pop("fn")
+        rec("lars_update+bf16", 22 * n, *upd16, "libgsync", plain_ms=upd[0], plain_again_ms=again[0],
+            ratio_to_plain=upd16[0] / upd[0], byte_ratio=22 / 20)
         both = timeit(lars_step, args.iters)  # one event pair around the two launches
         rec("lars_step", 28 * n, *both, "libgsync")
     plan.set_ptrs(2, ms)
@@ -192,6 +208,19 @@ def main():
         upd = timeit_plan(plan, lamb_step, args.iters, kind=L.GS_OP_LAMB, per=2)
         _LAST.pop("fn")  # the update is not launched alone: no batched figure for it
         rec("lamb_update", 16 * n, *upd, "libgsync")
+        # ... and with the bf16 copy of the new p (slot 4, gs_lamb_step_lowp), as lars_update+bf16
+        lowp16 = [torch.zeros(s, device=dev, dtype=torch.bfloat16) for s in shapes]  # kept, as above
+        plan.set_ptrs(4, lowp16)
+
+        def lamb_step_lowp():
+            lamb_moments()
+            plan.lamb(1e-6, *lamb_hp, nrm, lowp_dtype=torch.bfloat16)
+
+        upd16 = timeit_plan(plan, lamb_step_lowp, args.iters, kind=L.GS_OP_LAMB, per=2)
+        again = timeit_plan(plan, lamb_step, args.iters, kind=L.GS_OP_LAMB, per=2)
+        _LAST.pop("fn")
+        rec("lamb_update+bf16", 18 * n, *upd16, "libgsync", plain_ms=upd[0], plain_again_ms=again[0],
+            ratio_to_plain=upd16[0] / upd[0], byte_ratio=18 / 16)
         both = timeit(lamb_step, args.iters)  # one event pair around the two launches
         rec("lamb_step", 40 * n, *both, "libgsync")
     if not args.skip_torch and want("lamb"):

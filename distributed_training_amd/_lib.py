@@ -131,6 +131,8 @@ SIGNATURES = {
     "gs_plan_set_adapt": (_c_int, [_vp, _p_i32]),
     "gs_lars_norms": (_c_int, [_vp, _c_int, _vp, _vp]),
     "gs_lars_step": (_c_int, [_vp, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp, _vp]),
+    "gs_lars_step_lowp": (_c_int, [_vp, _c_int, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp, _vp]),
+    "gs_lamb_step_lowp": (_c_int, [_vp, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp]),
     "gs_lamb_moments": (_c_int, [_vp, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp, _vp]),
     "gs_lamb_step": (_c_int, [_vp, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp]),
     "gs_lamb_hyper": (_c_int, [_c_int, _vp, _vp, _c_d, _c_d, _c_int, _vp, _vp, _vp]),

@@ -14,7 +14,9 @@ TorchDDPPlugin -> libgsync DistributedDataParallel (+ fp16 autocast and the
 libgsync GradScaler for mixed_precision='fp16', the run.sh default).
 LowLevelZeroPlugin -> libgsync ZeRO (stage 1 default, fp16 params, fp32
 master, dynamic loss scale).  HybridAdam -> libgsync FusedAdam (AdamW mode,
-Colossal's default); Lamb / FusedLAMB -> libgsync FusedLAMB (TorchDDPPlugin only).  ColossalAI is not installed here: its numerics are
+Colossal's default); Lamb / FusedLAMB -> libgsync FusedLAMB (TorchDDPPlugin only);
+DistributedLamb -> the sharded LAMB step of libgsync ZeRO under LowLevelZeroPlugin (FusedLAMB
+under TorchDDPPlugin).  ColossalAI is not installed here: its numerics are
 restated from the published algorithm, parity unpinned.
 """
 from __future__ import annotations
@@ -128,6 +130,28 @@ class FusedLAMB(_FusedLAMB):
                          bias_correction=bias_correction, max_grad_norm=max_grad_norm or None,
                          capturable=bool(kw.pop("capturable", False)))
         self.set_grad_none = set_grad_none
+
+
+class DistributedLamb(_FusedLAMB):
+    """``colossalai.nn.optimizer.DistributedLamb``'s signature: the LAMB that ColossalAI
+    ships for its ZeRO plugin.  Under :class:`LowLevelZeroPlugin` it configures
+    libgsync's sharded LAMB step (``ZeroDataParallel(optimizer="lamb")``: per-tensor sums
+    of each rank's pieces, one all-reduce, the update); under :class:`TorchDDPPlugin` it
+    is plain FusedLAMB.  Every tensor is adapted, as :class:`Lamb`."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0, bias_correction=True, **kw):
+        params = list(params)
+        if params and not isinstance(params[0], dict):
+            params = [{"params": params}]
+        for g in params:
+            g.setdefault("adapt", True)
+        capturable = bool(kw.pop("capturable", False))  # not a Colossal argument: for CapturedStep
+        if kw:
+            raise TypeError(f"DistributedLamb: unsupported keyword arguments {sorted(kw)}")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                         bias_correction=bias_correction, capturable=capturable)
+        self.colossal_kwargs = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                                    bias_correction=bool(bias_correction))
 
 
 class _DPPluginBase:
@@ -267,11 +291,22 @@ class LowLevelZeroPlugin(_DPPluginBase):
 
     def configure(self, model, optimizer, mixed_precision):
         dtype = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}[self.precision]
-        if isinstance(optimizer, _FusedLAMB):
+        if isinstance(optimizer, _FusedLAMB) and not isinstance(optimizer, DistributedLamb):
             raise NotImplementedError(
                 "LAMB under ZeRO: a shard's norm would span ranks (LAMB's per-tensor trust ratio needs "
-                "whole tensors); use TorchDDPPlugin")
+                "whole tensors); use TorchDDPPlugin, or DistributedLamb")
         model = model.to(get_current_device()).to(dtype)
+        if isinstance(optimizer, DistributedLamb):
+            if len(optimizer.param_groups) != 1:
+                raise NotImplementedError("DistributedLamb under LowLevelZeroPlugin: one parameter group")
+            hp = optimizer.colossal_kwargs
+            scaler = DynamicLossScaler(**self.scaler_kw) if dtype == torch.float16 else None
+            zero = ZeroDataParallel(model, stage=self.stage, optimizer="lamb", lr=optimizer.param_groups[0]["lr"],
+                                    betas=hp["betas"], eps=hp["eps"], weight_decay=hp["weight_decay"],
+                                    bias_correction=hp["bias_correction"], adapt=optimizer.param_groups[0]["adapt"],
+                                    reduce_bucket_size=self.bucket, gradient_clipping=self.max_norm,
+                                    loss_scaler=scaler)
+            return _CastInputs(model, dtype), _ZeroOptimizerWrapper(zero)
         hp = getattr(optimizer, "colossal_kwargs", None) or dict(
             lr=optimizer.param_groups[0]["lr"], betas=optimizer.param_groups[0].get("betas", (0.9, 0.999)),
             eps=optimizer.param_groups[0].get("eps", 1e-8), weight_decay=optimizer.param_groups[0].get("weight_decay", 0.0),

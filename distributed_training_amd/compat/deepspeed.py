@@ -211,16 +211,29 @@ class DeepSpeedEngine(nn.Module):
         use_zero = stage in (1, 2) or dtype != torch.float32
         self._ddp = None
         self._zero = None
-        if kind == "lamb" and use_zero:
-            raise NotImplementedError(
-                "optimizer type Lamb under ZeRO or 16-bit training: a shard's norm would span ranks "
-                "(LAMB's per-tensor trust ratio needs whole tensors); use stage 0 in fp32")
+        lamb_kw = {}
+        if kind == "lamb":
+            if p.get("amsgrad", False) or p.get("eps_inside_sqrt", False):
+                raise NotImplementedError("Lamb: amsgrad / eps_inside_sqrt are not provided")
+            if use_zero and not config.get("zero_allow_untested_optimizer", False):
+                # DeepSpeed itself runs Lamb under ZeRO only behind this key
+                raise NotImplementedError(
+                    "optimizer type Lamb under ZeRO or 16-bit training: a shard's norm would span ranks "
+                    "(LAMB's per-tensor trust ratio needs whole tensors); use stage 0 in fp32, or set "
+                    "\"zero_allow_untested_optimizer\": true for the sharded LAMB step (one all-reduce of "
+                    "the per-tensor sums between its two passes)")
+            # DeepSpeed's FusedLamb: its names and defaults (max_coeff / min_coeff clamp the
+            # trust ratio), every tensor adapted, gradient_clipping as the pre-normalisation
+            lamb_kw = dict(adapt=True, bias_correction=p.get("bias_correction", True),
+                           min_trust=p.get("min_coeff", 0.01), max_trust=p.get("max_coeff", 10.0))
         if use_zero:
             self._zero = ZeroDataParallel(
                 self.module, stage=max(1, stage), optimizer=kind, lr=lr, betas=betas, eps=eps, weight_decay=wd,
+                **lamb_kw,
                 momentum=p.get("momentum", 0.0), reduce_bucket_size=int(zcfg.get("reduce_bucket_size", 5e8)
                                                                       if isinstance(zcfg, dict) else 5e8),
-                gradient_clipping=self.clip, loss_scaler=scaler,
+                gradient_clipping=self.clip or (p.get("max_grad_norm", 0.0) if kind == "lamb" else 0.0),
+                loss_scaler=scaler,
                 # libgsync extension keys (DeepSpeed ignores unknown ones): per-bucket parameter
                 # all-gathers under the next forward instead of DeepSpeed's end-of-step gather
                 overlap_allgather=bool(isinstance(zcfg, dict) and zcfg.get("overlap_allgather", False)),
@@ -233,14 +246,10 @@ class DeepSpeedEngine(nn.Module):
                 self.optimizer = FusedSGD(self.module.parameters(), lr=lr, momentum=p.get("momentum", 0.0),
                                           weight_decay=wd, max_grad_norm=self.clip or None)
             elif kind == "lamb":
-                # DeepSpeed's FusedLamb: its names and defaults (max_coeff / min_coeff clamp the
-                # trust ratio), every tensor adapted, gradient_clipping as the pre-normalisation
-                if p.get("amsgrad", False) or p.get("eps_inside_sqrt", False):
-                    raise NotImplementedError("Lamb: amsgrad / eps_inside_sqrt are not provided")
                 params = [{"params": list(self.module.parameters()), "adapt": True}]
                 self.optimizer = FusedLAMB(params, lr=lr, betas=betas, eps=eps, weight_decay=wd,
-                                           bias_correction=p.get("bias_correction", True),
-                                           min_trust=p.get("min_coeff", 0.01), max_trust=p.get("max_coeff", 10.0),
+                                           bias_correction=lamb_kw["bias_correction"],
+                                           min_trust=lamb_kw["min_trust"], max_trust=lamb_kw["max_trust"],
                                            max_grad_norm=self.clip or p.get("max_grad_norm", 0.0) or None)
             else:
                 self.optimizer = FusedAdam(self.module.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=wd,

@@ -1,1 +1,1 @@
-from distributed_training_amd.compat.colossalai import FusedLAMB, HybridAdam, Lamb  # noqa: F401
+from distributed_training_amd.compat.colossalai import DistributedLamb, FusedLAMB, HybridAdam, Lamb  # noqa: F401

@@ -404,11 +404,11 @@ int hip_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gs, 
              const ClipArgs* clip, void* stream);
 int hip_lars_set_adapt(gs_plan* p);  // upload p->adapt (allocates the LARS scratch on first use)
 int hip_lars_norms(gs_plan* p, int gdt, float* norms, void* stream);
-int hip_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gs, const float* fi,
+int hip_lars(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* norms, const float* gs, const float* fi,
              void* stream);
 int hip_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, const float* gs, const float* fi,
                      void* stream);
-int hip_lamb(gs_plan* p, const LambHyper& h, const float* norms, const float* fi, void* stream);
+int hip_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const float* fi, void* stream);
 int hip_lamb_hyper(double* step, const double* lr, double beta1, double beta2, int bias_correction,
                    const float* found_inf, float* hyper, void* stream);
 int hip_device_count();
@@ -431,9 +431,9 @@ int host_sgd(gs_plan* p, int gdt, int ldt, const SgdHyper& h, const float* gs, c
 int host_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gs, const float* fi,
               const ClipArgs* clip);
 int host_lars_norms(gs_plan* p, int gdt, float* norms);
-int host_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gs, const float* fi);
+int host_lars(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* norms, const float* gs, const float* fi);
 int host_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, const float* gs, const float* fi);
-int host_lamb(gs_plan* p, const LambHyper& h, const float* norms, const float* fi);
+int host_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const float* fi);
 // the clip coefficient of ClipArgs on the host (groups == 0: *sq is final)
 float host_clip_factor(const ClipArgs& c, const float* gs);
 // the device's 64-lane DPP fold (gs_kernels.hip wave_reduce) restated on the

@@ -1040,7 +1040,8 @@ struct SgdOp {
   }
 };
 
-// LARS (gs_lars_step): slots 0 = p (f32), 1 = g (GD), 2 = momentum buffer (f32).  SGD with
+// LARS (gs_lars_step / gs_lars_step_lowp): slots 0 = p (f32), 1 = g (GD), 2 = momentum buffer
+// (f32), 3 = low-precision copy of the new p (LD; LD < 0: no copy, no fourth stream).  SGD with
 // momentum whose learning rate and weight decay are per tensor: every lane forms its
 // tensor's (slr, wd) from the tensor's Σp², Σg² (gs_lars_norms) and adaptation flag —
 // on the full-chunk path the tensor index is wave-uniform, so that is a handful of
@@ -1048,7 +1049,7 @@ struct SgdOp {
 // launch sits between the norms and the update.  No fma anywhere: the contract
 // (include/gsync.h) rounds every multiply and add once.
 // NTG: non-temporal loads of the grad (false right behind gs_lars_norms when it fits the cache)
-template <int N, int GD, bool NTG = false>
+template <int N, int GD, int LD = -1, bool NTG = false>
 struct LarsOp {
   static constexpr int kN = N;
   static constexpr int kG = GS_G_SGD;
@@ -1068,7 +1069,9 @@ struct LarsOp {
   struct Frag { float p[N], g[N], b[N], slr, wd; };
   __device__ int phys(int k) const { return k; }
   __device__ bool active() const { return found_inf == nullptr || *found_inf == 0.f; }
-  __device__ bool fast_ok(const TV& v) const { return v.vec(0) && v.vec(1) && (h.mom == 0.f || v.vec(2)); }
+  __device__ bool fast_ok(const TV& v) const {
+    return v.vec(0) && v.vec(1) && (h.mom == 0.f || v.vec(2)) && (LD < 0 || v.vec(3));
+  }
   template <bool F>
   __device__ void load(const TV& v, int64_t e0, uint32_t lo, Frag& f) const {
     ld<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.p);
@@ -1094,17 +1097,19 @@ struct LarsOp {
     }
     st<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.p);
     if (h.mom != 0.f) st<GS_F32, N, F>(v.ptr[2], e0, lo, v.numel, v.vec(2), f.b);
+    if constexpr (LD >= 0) st<LD, N, F>(v.ptr[3], e0, lo, v.numel, v.vec(3), f.p);
   }
 };
 
-// LAMB's second pass (gs_lamb_step): slots 0 = p, 2 = exp_avg, 3 = exp_avg_sq (all f32), as
-// the moments pass left them.  Every lane forms its tensor's slr from the tensor's Σp², Σu²
+// LAMB's second pass (gs_lamb_step / gs_lamb_step_lowp): slots 0 = p, 2 = exp_avg,
+// 3 = exp_avg_sq (all f32), as the moments pass left them; 4 = low-precision copy of the
+// new p (LD; LD < 0: no copy).  Every lane forms its tensor's slr from the tensor's Σp², Σu²
 // (lamb_coef) and takes its wd_t once, in load; u is recomputed by the text the moments
 // pass summed (lamb_update).  No fma: the contract rounds every operation once.
 #ifndef GS_G_LAMB
 #define GS_G_LAMB 4
 #endif
-template <int N>
+template <int N, int LD = -1>
 struct LambOp {
   static constexpr int kN = N;
   static constexpr int kG = GS_G_LAMB;
@@ -1121,7 +1126,9 @@ struct LambOp {
   struct Frag { float p[N], m[N], v[N], slr, wd; };
   __device__ int phys(int k) const { return k; }
   __device__ bool active() const { return found_inf == nullptr || *found_inf == 0.f; }
-  __device__ bool fast_ok(const TV& tv) const { return tv.vec(0) && tv.vec(2) && tv.vec(3); }
+  __device__ bool fast_ok(const TV& tv) const {
+    return tv.vec(0) && tv.vec(2) && tv.vec(3) && (LD < 0 || tv.vec(4));
+  }
   template <bool F>
   __device__ void load(const TV& tv, int64_t e0, uint32_t lo, Frag& f) const {
     ld<GS_F32, N, F>(tv.ptr[0], e0, lo, tv.numel, tv.vec(0), f.p);
@@ -1137,6 +1144,7 @@ struct LambOp {
 #pragma unroll
     for (int i = 0; i < N; ++i) f.p[i] = f.p[i] - f.slr * lamb_update(h, f.p[i], f.m[i], f.v[i], f.wd);
     st<GS_F32, N, F>(tv.ptr[0], e0, lo, tv.numel, tv.vec(0), f.p);
+    if constexpr (LD >= 0) st<LD, N, F>(tv.ptr[4], e0, lo, tv.numel, tv.vec(4), f.p);
   }
 };
 
@@ -1266,14 +1274,14 @@ __device__ __forceinline__ void load_hyper(SgdOp<N, GD, LD, NTG>& op) {
   }
   load_grad_multiplier(op);
 }
-template <int N, int GD, bool NTG>
-__device__ __forceinline__ void load_hyper(LarsOp<N, GD, NTG>& op) {
+template <int N, int GD, int LD, bool NTG>
+__device__ __forceinline__ void load_hyper(LarsOp<N, GD, LD, NTG>& op) {
   if (op.hyper) op.h.lr = op.hyper[0];
   op.use_gs = op.gscale != nullptr;
   op.gsv = op.gscale ? *op.gscale : 1.f;
 }
-template <int N>
-__device__ __forceinline__ void load_hyper(LambOp<N>& op) {
+template <int N, int LD>
+__device__ __forceinline__ void load_hyper(LambOp<N, LD>& op) {
   if (op.hyper) {
     op.h.lr = op.hyper[0];
     op.h.bc1 = op.hyper[1];

@@ -408,7 +408,8 @@ int host_lars_norms(gs_plan* p, int gdt, float* norms) {
   return GS_OK;
 }
 
-int host_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gsc, const float* fi) {
+int host_lars(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* norms, const float* gsc,
+              const float* fi) {
   GS_TRY_RET(check_float(gdt));
   if (fi && fi[0] != 0.f) return GS_OK;
   const bool has_m = gsc != nullptr;
@@ -416,11 +417,12 @@ int host_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const
   std::vector<float> slr(p->n), wdt(p->n);
   for (int t = 0; t < p->n; ++t)
     lars_coef(h, norms[2 * t], norms[2 * t + 1], p->adapt.empty() ? 1 : p->adapt[t], has_m, m, &slr[t], &wdt[t]);
-  GS_HOST_FLOAT(gdt, GD, {
+  GS_HOST_FLOAT(gdt, GD, GS_HOST_LOWP(ldt, LD, {
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       float* pp = static_cast<float*>(slot(p, 0, t));
       const void* gp = slot(p, 1, t);
       float* bp = static_cast<float*>(slot(p, 2, t));
+      [[maybe_unused]] void* lp = slot(p, 3, t);
       const float lr_t = slr[t], wd_t = wdt[t];
       for (int64_t i = i0; i < i1; ++i) {
         float g = ldT<GD>(gp, i);
@@ -433,9 +435,10 @@ int host_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const
           d = b;
         }
         pp[i] = pp[i] - lr_t * d;
+        if constexpr (LD >= 0) stT<LD>(lp, i, pp[i]);
       }
     });
-  });
+  }));
   return GS_OK;
 }
 
@@ -482,7 +485,7 @@ int host_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, con
   return GS_OK;
 }
 
-int host_lamb(gs_plan* p, const LambHyper& h, const float* norms, const float* fi) {
+int host_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const float* fi) {
   if (fi && fi[0] != 0.f) return GS_OK;
   std::vector<float> slr(p->n), wdt(p->n);
   for (int t = 0; t < p->n; ++t) {
@@ -490,12 +493,18 @@ int host_lamb(gs_plan* p, const LambHyper& h, const float* norms, const float* f
     slr[t] = lamb_coef(h, norms[2 * t], norms[2 * t + 1], ad);
     wdt[t] = ad != 0 ? h.wd : 0.f;
   }
-  for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
-    float* pp = static_cast<float*>(slot(p, 0, t));
-    const float* mp = static_cast<const float*>(slot(p, 2, t));
-    const float* vp = static_cast<const float*>(slot(p, 3, t));
-    const float lr_t = slr[t], wd_t = wdt[t];
-    for (int64_t i = i0; i < i1; ++i) pp[i] = pp[i] - lr_t * lamb_update(h, pp[i], mp[i], vp[i], wd_t);
+  GS_HOST_LOWP(ldt, LD, {
+    for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
+      float* pp = static_cast<float*>(slot(p, 0, t));
+      const float* mp = static_cast<const float*>(slot(p, 2, t));
+      const float* vp = static_cast<const float*>(slot(p, 3, t));
+      [[maybe_unused]] void* lp = slot(p, 4, t);
+      const float lr_t = slr[t], wd_t = wdt[t];
+      for (int64_t i = i0; i < i1; ++i) {
+        pp[i] = pp[i] - lr_t * lamb_update(h, pp[i], mp[i], vp[i], wd_t);
+        if constexpr (LD >= 0) stT<LD>(lp, i, pp[i]);
+      }
+    });
   });
   return GS_OK;
 }

@@ -562,26 +562,55 @@ int gs_lars_norms(gs_plan* p, int grad_dtype, float* norms_out, void* stream) {
   return hip_lars_norms(p, grad_dtype, norms_out, stream);
 }
 
+// the low-precision copy of gs_lars_step_lowp / gs_lamb_step_lowp: -1 (none), bf16 or f16,
+// and then `slot` bound on every non-empty tensor
+static int lowp_slot_ok(const gs_plan* p, int lowp_dtype, int slot, const std::string& who) {
+  if (lowp_dtype == -1) return GS_OK;
+  if (lowp_dtype != GS_BF16 && lowp_dtype != GS_F16)
+    return fail(GS_EINVAL, who + ": lowp dtype must be bf16, f16 or -1 (none)");
+  for (int t = 0; t < p->n; ++t)
+    if (p->numel[t] > 0 && p->h_ptrs[static_cast<size_t>(slot) * p->n + t] == nullptr)
+      return fail(GS_EINVAL, who + ": slot " + std::to_string(slot) + " of tensor " + std::to_string(t) +
+                                 " is not bound");
+  return GS_OK;
+}
+
+static int lars_step(const char* who, gs_plan* p, int grad_dtype, int lowp_dtype, double lr, double momentum,
+                     double weight_decay, double trust_coefficient, double eps, const float* norms,
+                     const float* grad_scale_dev, const float* found_inf_dev, void* stream) {
+  const std::string w(who);
+  GsRange range(who);
+  PLAN_OK(p);
+  if (!is_float_dtype(grad_dtype)) return fail(GS_EINVAL, w + ": grad dtype must be f32, bf16 or f16");
+  if (p->n != 0 && norms == nullptr) return fail(GS_EINVAL, w + ": NULL norms");
+  if (!(momentum >= 0 && weight_decay >= 0 && trust_coefficient >= 0 && eps >= 0))
+    return fail(GS_EINVAL, w + ": momentum, weight_decay, trust_coefficient and eps must be >= 0");
+  if (p->clip_on)
+    return fail(GS_ESTATE, w + ": a gradient-norm clip is set on the plan (gs_plan_set_clip); "
+                               "clipping is not part of LARS");
+  LarsHyper h{static_cast<float>(lr), static_cast<float>(momentum), static_cast<float>(weight_decay),
+              static_cast<float>(trust_coefficient), static_cast<float>(eps)};
+  GS_TRY_RET(lars_slots_bound(p, h.mom != 0.f ? 3 : 2, who));
+  GS_TRY_RET(lowp_slot_ok(p, lowp_dtype, 3, w));
+  if (p->kind == GS_DEV_HOST) {
+    if (p->hyper) h.lr = p->hyper[0];
+    return host_lars(p, grad_dtype, lowp_dtype, h, norms, grad_scale_dev, found_inf_dev);
+  }
+  return hip_lars(p, grad_dtype, lowp_dtype, h, norms, grad_scale_dev, found_inf_dev, stream);
+}
+
 int gs_lars_step(gs_plan* p, int grad_dtype, double lr, double momentum, double weight_decay,
                  double trust_coefficient, double eps, const float* norms, const float* grad_scale_dev,
                  const float* found_inf_dev, void* stream) {
-  GsRange range("gs_lars_step");
-  PLAN_OK(p);
-  GS_CHECK_ARG(is_float_dtype(grad_dtype), "gs_lars_step: grad dtype must be f32, bf16 or f16");
-  GS_CHECK_ARG(p->n == 0 || norms != nullptr, "gs_lars_step: NULL norms");
-  GS_CHECK_ARG(momentum >= 0 && weight_decay >= 0 && trust_coefficient >= 0 && eps >= 0,
-               "gs_lars_step: momentum, weight_decay, trust_coefficient and eps must be >= 0");
-  if (p->clip_on)
-    return fail(GS_ESTATE, "gs_lars_step: a gradient-norm clip is set on the plan (gs_plan_set_clip); "
-                           "clipping is not part of LARS");
-  LarsHyper h{static_cast<float>(lr), static_cast<float>(momentum), static_cast<float>(weight_decay),
-              static_cast<float>(trust_coefficient), static_cast<float>(eps)};
-  GS_TRY_RET(lars_slots_bound(p, h.mom != 0.f ? 3 : 2, "gs_lars_step"));
-  if (p->kind == GS_DEV_HOST) {
-    if (p->hyper) h.lr = p->hyper[0];
-    return host_lars(p, grad_dtype, h, norms, grad_scale_dev, found_inf_dev);
-  }
-  return hip_lars(p, grad_dtype, h, norms, grad_scale_dev, found_inf_dev, stream);
+  return lars_step("gs_lars_step", p, grad_dtype, -1, lr, momentum, weight_decay, trust_coefficient, eps, norms,
+                   grad_scale_dev, found_inf_dev, stream);
+}
+
+int gs_lars_step_lowp(gs_plan* p, int grad_dtype, int lowp_dtype, double lr, double momentum,
+                      double weight_decay, double trust_coefficient, double eps, const float* norms,
+                      const float* grad_scale_dev, const float* found_inf_dev, void* stream) {
+  return lars_step("gs_lars_step_lowp", p, grad_dtype, lowp_dtype, lr, momentum, weight_decay, trust_coefficient,
+                   eps, norms, grad_scale_dev, found_inf_dev, stream);
 }
 
 static int lamb_args_ok(const gs_plan* p, double eps, double wd, double bc1, double bc2s, const char* who) {
@@ -616,18 +645,21 @@ int gs_lamb_moments(gs_plan* p, int grad_dtype, double beta1, double beta2, doub
   return hip_lamb_moments(p, grad_dtype, h, norms_out, grad_scale_dev, found_inf_dev, stream);
 }
 
-int gs_lamb_step(gs_plan* p, double lr, double eps, double weight_decay, double bc1, double bc2_sqrt,
-                 double min_ratio, double max_ratio, const float* norms, const float* found_inf_dev, void* stream) {
-  GsRange range("gs_lamb_step");
+static int lamb_step(const char* who, gs_plan* p, int lowp_dtype, double lr, double eps, double weight_decay,
+                     double bc1, double bc2_sqrt, double min_ratio, double max_ratio, const float* norms,
+                     const float* found_inf_dev, void* stream) {
+  const std::string w(who);
+  GsRange range(who);
   PLAN_OK(p);
-  GS_CHECK_ARG(p->n == 0 || norms != nullptr, "gs_lamb_step: NULL norms");
-  GS_CHECK_ARG(min_ratio >= 0 && max_ratio >= min_ratio, "gs_lamb_step: 0 <= min_ratio <= max_ratio");
-  GS_TRY_RET(lamb_args_ok(p, eps, weight_decay, bc1, bc2_sqrt, "gs_lamb_step"));
+  if (p->n != 0 && norms == nullptr) return fail(GS_EINVAL, w + ": NULL norms");
+  if (!(min_ratio >= 0 && max_ratio >= min_ratio)) return fail(GS_EINVAL, w + ": 0 <= min_ratio <= max_ratio");
+  GS_TRY_RET(lamb_args_ok(p, eps, weight_decay, bc1, bc2_sqrt, who));
   for (int t = 0; t < p->n; ++t)
     for (int s : {0, 2, 3})
       if (p->numel[t] > 0 && p->h_ptrs[static_cast<size_t>(s) * p->n + t] == nullptr)
-        return fail(GS_EINVAL, "gs_lamb_step: slot " + std::to_string(s) + " of tensor " + std::to_string(t) +
+        return fail(GS_EINVAL, w + ": slot " + std::to_string(s) + " of tensor " + std::to_string(t) +
                                    " is not bound");
+  GS_TRY_RET(lowp_slot_ok(p, lowp_dtype, 4, w));
   LambHyper h = make_lamb(0.0, 0.0, bc1, bc2_sqrt, eps, weight_decay, lr, min_ratio, max_ratio);
   if (p->kind == GS_DEV_HOST) {
     if (p->hyper) {
@@ -635,9 +667,22 @@ int gs_lamb_step(gs_plan* p, double lr, double eps, double weight_decay, double 
       h.bc1 = p->hyper[1];
       h.bc2s = p->hyper[2];
     }
-    return host_lamb(p, h, norms, found_inf_dev);
+    return host_lamb(p, lowp_dtype, h, norms, found_inf_dev);
   }
-  return hip_lamb(p, h, norms, found_inf_dev, stream);
+  return hip_lamb(p, lowp_dtype, h, norms, found_inf_dev, stream);
+}
+
+int gs_lamb_step(gs_plan* p, double lr, double eps, double weight_decay, double bc1, double bc2_sqrt,
+                 double min_ratio, double max_ratio, const float* norms, const float* found_inf_dev, void* stream) {
+  return lamb_step("gs_lamb_step", p, -1, lr, eps, weight_decay, bc1, bc2_sqrt, min_ratio, max_ratio, norms,
+                   found_inf_dev, stream);
+}
+
+int gs_lamb_step_lowp(gs_plan* p, int lowp_dtype, double lr, double eps, double weight_decay, double bc1,
+                      double bc2_sqrt, double min_ratio, double max_ratio, const float* norms,
+                      const float* found_inf_dev, void* stream) {
+  return lamb_step("gs_lamb_step_lowp", p, lowp_dtype, lr, eps, weight_decay, bc1, bc2_sqrt, min_ratio, max_ratio,
+                   norms, found_inf_dev, stream);
 }
 
 int gs_lamb_hyper(int device_kind, double* step, const double* lr, double beta1, double beta2, int bias_correction,

@@ -1,5 +1,5 @@
 // gfx950 (CDNA4) fused SGD / Adam(W) / LARS updates of libgsync (gs_sgd_step / gs_adam_step /
-// gs_lars_step): the chunk-map engine of gs_engine.h with SgdOp / AdamOp / LarsOp, the
+// gs_lars_step[_lowp]): the chunk-map engine of gs_engine.h with SgdOp / AdamOp / LarsOp, the
 // grad-load policy per launch; LARS's per-tensor Σp², Σg² (gs_lars_norms), a segmented
 // reduction over the same chunk map; and LAMB (gs_lamb_moments / gs_lamb_step): that
 // reduction fused with the moments' read-modify-write, then LambOp on the engine.
@@ -377,25 +377,26 @@ int hip_lars_norms(gs_plan* p, int gdt, float* norms, void* stream) {
   });
 }
 
+// ldt = -1: LarsOp<.., -1, ..>, the op without a copy stream (gs_lars_step)
 template <bool NTG>
-static int lars_nt(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gsc, const float* fi,
-                   void* stream) {
-  GS_DISPATCH_FLOAT(gdt, GD, {
-    LarsOp<kUnit, GD, NTG> op;
+static int lars_nt(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* norms, const float* gsc,
+                   const float* fi, void* stream) {
+  GS_DISPATCH_FLOAT(gdt, GD, GS_DISPATCH_LOWP(ldt, LD, {
+    LarsOp<kUnit, GD, LD, NTG> op;
     op.h = h; op.norms = norms; op.adapt = reinterpret_cast<const int32_t*>(lars_adapt_ptr(p));
     op.gscale = gsc; op.found_inf = fi; op.hyper = p->hyper;
     return launch(p, op, stream);
-  });
+  }));
   return GS_OK;
 }
 
-int hip_lars(gs_plan* p, int gdt, const LarsHyper& h, const float* norms, const float* gsc, const float* fi,
-             void* stream) {
+int hip_lars(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* norms, const float* gsc,
+             const float* fi, void* stream) {
   DeviceGuard g(p->device);
   if (p->n == 0) return GS_OK;
   GS_TRY_RET(lars_prepare(p, stream));
-  return nt_grad(p, gdt) ? lars_nt<true>(p, gdt, h, norms, gsc, fi, stream)
-                         : lars_nt<false>(p, gdt, h, norms, gsc, fi, stream);
+  return nt_grad(p, gdt) ? lars_nt<true>(p, gdt, ldt, h, norms, gsc, fi, stream)
+                         : lars_nt<false>(p, gdt, ldt, h, norms, gsc, fi, stream);
 }
 
 // ------------------------------------------------------------------- LAMB
@@ -626,14 +627,17 @@ int hip_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, cons
   });
 }
 
-int hip_lamb(gs_plan* p, const LambHyper& h, const float* norms, const float* fi, void* stream) {
+int hip_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const float* fi, void* stream) {
   DeviceGuard g(p->device);
   if (p->n == 0) return GS_OK;
   GS_TRY_RET(lars_prepare(p, stream));
-  LambOp<kUnit> op;
-  op.h = h; op.norms = norms; op.adapt = reinterpret_cast<const int32_t*>(lars_adapt_ptr(p));
-  op.found_inf = fi; op.hyper = p->hyper;
-  return launch(p, op, stream);
+  GS_DISPATCH_LOWP(ldt, LD, {
+    LambOp<kUnit, LD> op;
+    op.h = h; op.norms = norms; op.adapt = reinterpret_cast<const int32_t*>(lars_adapt_ptr(p));
+    op.found_inf = fi; op.hyper = p->hyper;
+    return launch(p, op, stream);
+  });
+  return GS_OK;
 }
 
 }  // namespace gs

@@ -281,10 +281,21 @@ class TensorListPlan:
                 "gs_lars_norms")
 
     def lars(self, grad_dtype, lr, momentum, weight_decay, trust_coefficient, eps, norms: torch.Tensor,
-             grad_scale=None, found_inf=None, stream=None):
+             grad_scale=None, found_inf=None, stream=None, lowp_dtype=None):
         """The LARS update on slots 0 = p, 1 = g, 2 = momentum buffer with the
-        per-tensor sums of :meth:`lars_norms` (gs_lars_step)."""
+        per-tensor sums of :meth:`lars_norms` (gs_lars_step); with ``lowp_dtype``
+        (bf16 / fp16) it also writes slot 3 = that copy of the new p (gs_lars_step_lowp)."""
         self._norms_ok(norms)
+        if lowp_dtype is not None:
+            L.check(
+                L.lib().gs_lars_step_lowp(
+                    self.handle, L.gs_dtype(grad_dtype), L.gs_dtype(lowp_dtype), float(lr), float(momentum),
+                    float(weight_decay), float(trust_coefficient), float(eps), norms.data_ptr(),
+                    None if grad_scale is None else grad_scale.data_ptr(),
+                    None if found_inf is None else found_inf.data_ptr(), self._stream(stream)),
+                "gs_lars_step_lowp",
+            )
+            return
         L.check(
             L.lib().gs_lars_step(
                 self.handle, L.gs_dtype(grad_dtype), float(lr), float(momentum), float(weight_decay),
@@ -312,11 +323,21 @@ class TensorListPlan:
         )
 
     def lamb(self, lr, eps, wd, bc1, bc2s, norms: torch.Tensor, min_ratio=0.0, max_ratio=float("inf"),
-             found_inf=None, stream=None):
+             found_inf=None, stream=None, lowp_dtype=None):
         """LAMB's second pass on slots 0, 2, 3 with the sums of :meth:`lamb_moments`
         (same eps, wd, bc1, bc2s): p -= lr * clamp(‖p‖/‖u‖, min_ratio, max_ratio) * u,
-        u recomputed from the stored moments (gs_lamb_step)."""
+        u recomputed from the stored moments (gs_lamb_step); with ``lowp_dtype`` (bf16 /
+        fp16) it also writes slot 4 = that copy of the new p (gs_lamb_step_lowp)."""
         self._norms_ok(norms)
+        if lowp_dtype is not None:
+            L.check(
+                L.lib().gs_lamb_step_lowp(
+                    self.handle, L.gs_dtype(lowp_dtype), float(lr), float(eps), float(wd), float(bc1), float(bc2s),
+                    float(min_ratio), float(max_ratio), norms.data_ptr(),
+                    None if found_inf is None else found_inf.data_ptr(), self._stream(stream)),
+                "gs_lamb_step_lowp",
+            )
+            return
         L.check(
             L.lib().gs_lamb_step(
                 self.handle, float(lr), float(eps), float(wd), float(bc1), float(bc2s), float(min_ratio),

@@ -412,8 +412,9 @@ class FusedLARS(_FusedBase):
     ``capturable=True`` with :meth:`refresh_hyper` lets ``graphs.CapturedStep``
     record it (take one eager step first: state and scratch must exist).
 
-    Out of scope: ZeRO shards (a tensor's norm would span ranks),
-    ``max_grad_norm``, nesterov, ``DDP._register_fused_optim``.
+    Under ZeRO-1/2 or with a 16-bit model, LARS is ``ZeroDataParallel(optimizer="lars")``
+    (zero.py: per-tensor sums of each rank's pieces, one all-reduce of them).
+    Out of scope here: ``max_grad_norm``, nesterov, ``DDP._register_fused_optim``.
     """
 
     def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=0.0, trust_coefficient=1e-3, eps=1e-8,
@@ -739,8 +740,9 @@ class FusedLAMB(_DeviceSteps, _FusedBase):
     ``capturable=True`` with :meth:`refresh_hyper` lets ``graphs.CapturedStep``
     record it (take one eager step first: state and scratch must exist).
 
-    Out of scope: ZeRO shards (a tensor's norm would span ranks),
-    ``DDP._register_fused_optim``, amsgrad, low-precision parameter copies.
+    Under ZeRO-1/2 or with a 16-bit model, LAMB is ``ZeroDataParallel(optimizer="lamb")``
+    (zero.py: per-tensor sums of each rank's pieces, one all-reduce of them).
+    Out of scope here: ``DDP._register_fused_optim``, amsgrad.
     """
 
     _name = "FusedLAMB"

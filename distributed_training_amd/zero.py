@@ -17,6 +17,12 @@ step:     (fp16) non-finite check of the shard + MAX all-reduce of the flag,
           launch); ONE fused Adam/SGD launch over all shards
           that also writes the low-precision params into this rank's slice
           of the param flat buffer; in-place all-gather of each bucket.
+          optimizer="lamb" / "lars" (layer-wise trust ratios): a second plan over the
+          PIECES of the parameters that fall into this rank's shard; its first pass
+          (gs_lamb_moments / gs_lars_norms) leaves the pieces' partial Σp², Σu² (Σg²),
+          ONE SUM all-reduce of that fp32[2n] vector makes them the whole tensors'
+          (identical bits on every rank), the update (gs_lamb_step_lowp /
+          gs_lars_step_lowp) forms every ratio from it and writes master + model copy.
 No host synchronisation except the fp16 loss-scale bookkeeping (DeepSpeed
 reads its overflow flag on the host too).
 
@@ -80,15 +86,28 @@ class DynamicLossScaler:
         self.__dict__.update(sd)
 
 
+KINDS = ("adam", "adamw", "sgd", "lamb", "lars")
+
+
 class ZeroDataParallel:
     def __init__(self, module: torch.nn.Module, *, stage: int = 2, optimizer: str = "adamw", lr: float = 1e-3,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, momentum: float = 0.0,
                  process_group=None, reduce_bucket_size: int = int(5e7), gradient_clipping: float = 0.0,
                  loss_scaler: DynamicLossScaler | None = None, broadcast_params: bool = True,
                  capturable: bool = False, overlap_allgather: bool = False,
-                 allgather_bucket_size: int | None = None, communicator=None):
+                 allgather_bucket_size: int | None = None, communicator=None,
+                 adapt=None, bias_correction: bool = True, min_trust: float = 0.0, max_trust: float = math.inf,
+                 trust_coefficient: float = 1e-3):
+        """optimizer: "adam" | "adamw" | "sgd" | "lamb" | "lars".  The last five keywords
+        belong to "lamb" / "lars" and are ignored by the others: ``adapt`` says which
+        tensors get the trust ratio and weight decay (None: ``p.ndim > 1``; a bool for
+        all; or ``len(params)`` bools, a whole tensor's flag holding for its pieces);
+        ``bias_correction``, ``min_trust`` / ``max_trust`` (the ratio's clamp) are LAMB's,
+        ``trust_coefficient`` is LARS's (with ``momentum``)."""
         if stage not in (1, 2):
             raise NotImplementedError(f"ZeRO stage {stage}: only 1 and 2 are on the gradient-sync path")
+        if optimizer not in KINDS:
+            raise ValueError(f"ZeroDataParallel: optimizer {optimizer!r} is not one of {KINDS}")
         if not dist.is_initialized():
             raise RuntimeError("ZeroDataParallel needs an initialised process group")
         self.module = module
@@ -104,6 +123,19 @@ class ZeroDataParallel:
         self.device = self.params[0].device
         self.is_cuda = self.device.type == "cuda"
         self.kind = optimizer
+        self.layerwise = optimizer in ("lamb", "lars")
+        n_p = len(self.params)
+        if adapt is None:
+            self.adapt = [p.ndim > 1 for p in self.params]
+        elif isinstance(adapt, bool):
+            self.adapt = [adapt] * n_p
+        else:
+            self.adapt = [bool(a) for a in adapt]
+            if len(self.adapt) != n_p:
+                raise ValueError(f"adapt: {n_p} flags expected (one per parameter), got {len(self.adapt)}")
+        self.bias_correction = bool(bias_correction)
+        self.min_trust, self.max_trust = float(min_trust), float(max_trust)
+        self.trust_coefficient = float(trust_coefficient)
         self.hp = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, momentum=momentum)
         self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, momentum=momentum,
                                   params=self.params)]
@@ -113,6 +145,9 @@ class ZeroDataParallel:
         # capturable (CapturedStep): Adam's step counter, lr and bias corrections live on
         # the device (gs_adam_hyper advances them per launch, also on graph replays)
         self.capturable = bool(capturable)
+        if self.capturable and self.layerwise:
+            raise NotImplementedError(f"capturable ZeRO with {optimizer!r}: graph capture of the per-tensor sums' "
+                                      "all-reduce between the two passes is not supported")
         if self.capturable and (loss_scaler is not None or optimizer == "sgd"):
             raise NotImplementedError("capturable ZeRO: Adam/AdamW without a dynamic loss scaler "
                                       "(DeepSpeed's overflow check reads the flag on the host)")
@@ -272,16 +307,61 @@ class ZeroDataParallel:
         else:
             self.master = self.param_shards  # fp32 model: the shard IS the master copy
         self.state1 = [torch.zeros(s, dtype=torch.float32, device=self.device) for s in shard_sizes]
-        self.state2 = [torch.zeros(s, dtype=torch.float32, device=self.device) for s in shard_sizes]
+        # the second state: Adam's / LAMB's exp_avg_sq; sgd and lars have none (lars: not even
+        # allocated, its checkpoint writes zeros in that place)
+        self.state2 = [] if self.kind == "lars" else [
+            torch.zeros(s, dtype=torch.float32, device=self.device) for s in shard_sizes]
         self.plan = TensorListPlan(shard_sizes, self.device, task_units=update_task_units(self.device))
         self.plan.set_ptrs(0, self.master)
         self.plan.set_ptrs(1, self.grad_shards)
         self.plan.set_ptrs(2, self.state1)
         if self.kind == "sgd":
             self.plan.set_ptrs(3, self.param_shards if self.lowp else [0] * len(shard_sizes))
-        else:
+        elif self.kind != "lars":
             self.plan.set_ptrs(3, self.state2)
             self.plan.set_ptrs(4, self.param_shards if self.lowp else [0] * len(shard_sizes))
+        self.piece_plan = None
+        if self.layerwise:
+            self._build_piece_plan()
+
+    def shard_pieces(self, rank: int | None = None):
+        """[(bucket, offset in that rank's shard, numel)] per parameter, in ``self.params``
+        order: the intersection of the parameter's range in its bucket with the rank's
+        shard [rank*s_b, (rank+1)*s_b) (numel 0 where they do not meet).  A tensor lives
+        in one bucket and a rank's shard of a bucket is one range, so a rank holds at
+        most one piece of any tensor; the bucket's tail padding belongs to none."""
+        rank = self.rank if rank is None else rank
+        out = []
+        for i, p in enumerate(self.params):
+            b, off = self.loc[i]
+            lo = rank * self.shard_sizes[b]
+            a, e = max(off, lo), min(off + p.numel(), lo + self.shard_sizes[b])
+            out.append((b, a - lo, e - a) if e > a else (b, 0, 0))
+        return out
+
+    def _build_piece_plan(self):
+        """The LAMB / LARS plan: entry i = this rank's piece of parameter i (0 elements
+        for a tensor it holds nothing of), so the per-tensor sums are indexed by the
+        global parameter index on every rank and one SUM all-reduce of fp32[2n]
+        completes them; the adapt flags are the whole tensors'."""
+        pieces = self.shard_pieces()
+        self.piece_plan = TensorListPlan([n for _, _, n in pieces], self.device,
+                                         task_units=update_task_units(self.device))
+
+        def ptrs(bufs):
+            return [bufs[b].data_ptr() + o * bufs[b].element_size() if n else 0 for b, o, n in pieces]
+
+        self.piece_plan.set_ptrs(0, ptrs(self.master))
+        self.piece_plan.set_ptrs(1, ptrs(self.grad_shards))
+        self.piece_plan.set_ptrs(2, ptrs(self.state1))
+        if self.kind == "lamb":
+            self.piece_plan.set_ptrs(3, ptrs(self.state2))
+            if self.lowp:
+                self.piece_plan.set_ptrs(4, ptrs(self.param_shards))
+        elif self.lowp:
+            self.piece_plan.set_ptrs(3, ptrs(self.param_shards))
+        self.piece_plan.set_adapt(self.adapt)
+        self._norms = torch.zeros(2 * len(pieces), dtype=torch.float32, device=self.device)
 
     # ---- watchdog marks of the step-end collectives (DESIGN §11.3): the reduce-scatters
     # and the clip's / overflow check's all-reduces hand their marks to the update's
@@ -293,11 +373,13 @@ class ZeroDataParallel:
         if self._comm is None or not self.is_cuda:
             self._mark_update = self._mark_next_pack = None
             return
-        L.check(L.lib().gs_bucketer_set_mark_consumer(self.handle, self.plan.handle if on else None),
+        # lamb / lars: the update is the piece plan's launch
+        upd = (self.piece_plan if self.piece_plan is not None else self.plan).handle
+        L.check(L.lib().gs_bucketer_set_mark_consumer(self.handle, upd if on else None),
                 "gs_bucketer_set_mark_consumer")
         first = ctypes.c_void_p()
         L.check(L.lib().gs_bucketer_first_pack_plan(self.handle, ctypes.byref(first)), "gs_bucketer_first_pack_plan")
-        self._mark_update = self.plan.handle if on else None
+        self._mark_update = upd if on else None
         self._mark_next_pack = first if on and first.value else None
 
     def set_mark_packets(self, packets: bool):
@@ -474,7 +556,7 @@ class ZeroDataParallel:
             found_inf.zero_()
             self.plan.unscale_check(1, self.dtype, None, found_inf)
             self._allreduce_scalar(found_inf, "max", consumer=self._mark_update)
-        if self.clip > 0 and _optim.CLIP_FUSED:
+        if self.clip > 0 and _optim.CLIP_FUSED and not self.layerwise:
             # DeepSpeed gradient_clipping (R:resnet/deepspeed/deepspeed_train.py:195) folded
             # into the update: its workgroups form min(1, c/(‖g‖+1e-6))·(1/scale) themselves
             # (gs_plan_set_clip) — no combine launch, no coefficient launch
@@ -499,6 +581,8 @@ class ZeroDataParallel:
                 self.plan.set_clip_groups(self.clip, 1e-6, gr, gr.numel(), inv_scale * inv_scale, inv_scale,
                                           out=s[4:7])
         elif self.clip > 0:
+            # (always for lamb / lars: they refuse a plan clip by contract, the clip
+            # coefficient goes in as their grad multiplier)
             self.plan.set_clip(None)
             sq = s[1:2]
             self.plan.sqnorm(1, self.dtype, sq)
@@ -518,6 +602,26 @@ class ZeroDataParallel:
         if self.kind == "sgd":
             self.plan.sgd(self.dtype, g0["lr"], g0["momentum"], 0.0, g0["weight_decay"], False, False,
                           self.step_count == 1, lowp_dtype=lowp, grad_scale=grad_scale, found_inf=found_inf)
+        elif self.kind == "lamb":
+            # pass 1 on this rank's pieces: new moments, partial Σp², Σu² per tensor; their SUM
+            # over the ranks (one small message; every rank then holds the same bits, so every
+            # rank forms the same ratios); pass 2 writes master and the model copy
+            pp, norms = self.piece_plan, self._norms
+            b1, b2 = g0["betas"]
+            bc1 = 1 - b1 ** self.step_count if self.bias_correction else 1.0
+            bc2s = (1 - b2 ** self.step_count) ** 0.5 if self.bias_correction else 1.0
+            pp.lamb_moments(self.dtype, b1, b2, g0["eps"], g0["weight_decay"], bc1, bc2s, norms,
+                            grad_scale=grad_scale, found_inf=found_inf)
+            self._allreduce_scalar(norms, "sum", consumer=self._mark_update)
+            pp.lamb(g0["lr"], g0["eps"], g0["weight_decay"], bc1, bc2s, norms, self.min_trust, self.max_trust,
+                    found_inf=found_inf, lowp_dtype=lowp)
+        elif self.kind == "lars":
+            # state1 is the momentum buffer; there is no second state
+            pp, norms = self.piece_plan, self._norms
+            pp.lars_norms(self.dtype, norms)
+            self._allreduce_scalar(norms, "sum", consumer=self._mark_update)
+            pp.lars(self.dtype, g0["lr"], g0["momentum"], g0["weight_decay"], self.trust_coefficient, g0["eps"],
+                    norms, grad_scale=grad_scale, found_inf=found_inf, lowp_dtype=lowp)
         elif self.capturable:
             # device hyper-parameters: advance the step, form [step_size, bc2_sqrt, 1 - lr*wd]
             # (the same double arithmetic as the host branch, T:optim/adam.py), the kernel reads them
@@ -590,13 +694,27 @@ class ZeroDataParallel:
         """‖g‖ of the unscaled averaged grads at the last clipped step (device tensor)."""
         return self._scratch[6:7]
 
+    def sq_norms(self):
+        """(params, norms) of the last lamb / lars step: norms[2i], norms[2i+1] = Σp² and
+        Σu² (lamb) / Σg² (lars) of parameter i, summed over the ranks' pieces — the
+        all-reduced vector the update read, identical on every rank (a device tensor;
+        as FusedLAMB.sq_norms())."""
+        if not self.layerwise:
+            raise RuntimeError(f"sq_norms(): optimizer {self.kind!r} forms no per-tensor sums")
+        return self.params, self._norms
+
     def state_dict(self):
         """This rank's optimizer shard (fp32 master + states): DeepSpeed's
-        zero_pp_rank_<r>_mp_rank_00_optim_states layout, one file per rank."""
+        zero_pp_rank_<r>_mp_rank_00_optim_states layout, one file per rank.
+        The layout is the same for every kind: "exp_avg" is the first state (lars,
+        sgd: the momentum buffer), "exp_avg_sq" the second (sgd: its unused zeros; lars
+        keeps none and writes zeros of the same shape)."""
         return {"step": self.device_step_count(), "rank": self.rank, "world": self.world, "stage": self.stage,
                 "bucket_numel": list(self.bucket_numel), "kind": self.kind,
                 "master": [m.detach().float().cpu().clone() for m in self.master],
-                "exp_avg": [t.cpu() for t in self.state1], "exp_avg_sq": [t.cpu() for t in self.state2],
+                "exp_avg": [t.cpu() for t in self.state1],
+                "exp_avg_sq": [t.cpu() for t in self.state2] if self.kind != "lars" else [
+                    torch.zeros(s, dtype=torch.float32) for s in self.shard_sizes],
                 "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
                 "loss_scaler": None if self.scaler is None else self.scaler.state_dict()}
 
@@ -697,6 +815,7 @@ class ZeroDataParallel:
 
     def close(self):
         self.wait_allgather()
+        pp = getattr(self, "piece_plan", None)
         if getattr(self, "handle", None) is not None and self.handle.value and self._comm is not None:
             self._bind_marks(False)  # no mark left on the update plan's or the pack plan's next launch
         for h in self._hooks + getattr(self, "_ag_hooks", []):
@@ -711,6 +830,9 @@ class ZeroDataParallel:
         if getattr(self, "handle", None) is not None and self.handle.value:
             L.destroy("gs_bucketer_destroy", self.handle)
             self.handle = None
+        if pp is not None:
+            pp.close()
+            self.piece_plan = None
 
 
 def warmup_lr(step: int, min_lr: float, max_lr: float, warmup_num_steps: int, warmup_type: str = "log") -> float:

@@ -372,9 +372,15 @@ int gs_adam_step(gs_plan* p, int grad_dtype, int lowp_dtype, double lr, double b
  * hold the same averaged grads form the same ratios and stay bit-identical.  The
  * host backend's order is fixed too (element order) but is not the device's.
  *
+ * Sharded tensors (ZeRO): a plan may hold the pieces of tensors that fall into one
+ * rank's shard (entries of 0 elements for tensors the rank holds nothing of).  The
+ * sums of a piece are partial; the caller SUM-all-reduces the fp32[2n] vector between
+ * gs_lars_norms and the update, after which every rank holds the same bits and forms
+ * the same ratios.  The order stays fixed: per rank by its plan, across ranks by the
+ * collective's.
+ *
  * Not part of LARS here: gradient-norm clipping (a clip set on the plan is
- * GS_ESTATE), nesterov, low-precision parameter copies, sharded tensors (a ZeRO
- * shard's norm would span ranks).
+ * GS_ESTATE), nesterov.
  *
  * gs_plan_set_adapt: per-tensor adaptation flags (int32[n], host memory), static
  * for the plan; default all 1.  Not capturable (it uploads synchronously); on a
@@ -398,6 +404,17 @@ int gs_lars_norms(gs_plan* p, int grad_dtype, float* norms_out, void* stream);
 int gs_lars_step(gs_plan* p, int grad_dtype, double lr, double momentum, double weight_decay,
                  double trust_coefficient, double eps, const float* norms,
                  const float* grad_scale_dev, const float* found_inf_dev, void* stream);
+/* gs_lars_step that also writes slot 3 = a low-precision copy of the new p (lowp_dtype
+ * GS_BF16 / GS_F16; -1 = none, and then this IS gs_lars_step: the same kernel).  The
+ * fp32 arithmetic is gs_lars_step's, unchanged; p_lowp[i] = cast(p_new[i]), round to
+ * nearest even, as gs_sgd_step / gs_adam_step write theirs.  The copy pointer may be
+ * 2-byte aligned (a stream that is not 16-B aligned takes the element-wise path).
+ * *found_inf != 0 writes nothing, the copy included.  A clip on the plan stays GS_ESTATE.
+ * replaces: the `p_lowp.copy_(p_master)` (torch._foreach_copy_) behind a Python LARS on
+ *           fp32 master weights (DeepSpeed / ColossalAI mixed-precision optimizers) */
+int gs_lars_step_lowp(gs_plan* p, int grad_dtype, int lowp_dtype, double lr, double momentum,
+                      double weight_decay, double trust_coefficient, double eps, const float* norms,
+                      const float* grad_scale_dev, const float* found_inf_dev, void* stream);
 /* Step-varying hyper-parameters from memory instead of the arguments: with a
  * non-NULL source, every later gs_sgd_step / gs_adam_step on this plan reads
  *   SGD:  hyper[0] = lr; hyper[1] = "first step" flag (buf = g) when gs_sgd_step
@@ -457,8 +474,8 @@ int gs_adam_hyper(int device_kind, double* step, const double* lr, double beta1,
  * a global pre-normalisation of the grads goes in as grad_scale_dev.  With a hyper
  * source on the plan (gs_plan_set_hyper_source) both kernels read hyper = [lr, bc1, bc2s]
  * from it when they run, as Adam reads its own; the argument values are then ignored.
- * Determinism: as gs_lars_norms.  Not part of LAMB here: amsgrad, low-precision parameter
- * copies, sharded tensors (a ZeRO shard's norm would span ranks).
+ * Determinism: as gs_lars_norms; sharded tensors as there (the caller SUM-all-reduces
+ * the vector between the two passes).  Not part of LAMB here: amsgrad, a plan clip.
  *
  * norms_out: fp32[2n] in the plan's memory kind: [2t] = Σp², [2t+1] = Σu² of tensor t.
  * Two launches (the chunk pass, the per-tensor fold), one timer record (GS_OP_LAMB_MOMENTS).
@@ -473,6 +490,15 @@ int gs_lamb_moments(gs_plan* p, int grad_dtype, double beta1, double beta2, doub
  *           p.add_(update, alpha=-lr*ratio) */
 int gs_lamb_step(gs_plan* p, double lr, double eps, double weight_decay, double bc1, double bc2_sqrt,
                  double min_ratio, double max_ratio, const float* norms, const float* found_inf_dev, void* stream);
+/* gs_lamb_step that also writes slot 4 = a low-precision copy of the new p (lowp_dtype
+ * GS_BF16 / GS_F16; -1 = none, and then this IS gs_lamb_step: the same kernel).  The fp32
+ * arithmetic is unchanged; p_lowp[i] = cast(p_new[i]), round to nearest even; the copy
+ * pointer may be 2-byte aligned; *found_inf != 0 writes nothing, the copy included.
+ * replaces: the `p_lowp.copy_(p_master)` behind a Python LAMB on fp32 master weights
+ *           (ColossalAI DistributedLamb under its mixed-precision ZeRO optimizer) */
+int gs_lamb_step_lowp(gs_plan* p, int lowp_dtype, double lr, double eps, double weight_decay,
+                      double bc1, double bc2_sqrt, double min_ratio, double max_ratio,
+                      const float* norms, const float* found_inf_dev, void* stream);
 /* LAMB hyper source update on the stream (one thread; graph-capturable), gs_adam_hyper's
  * counterpart:
  *   if (!found_inf || *found_inf == 0) *step += 1;
