@@ -9,11 +9,18 @@ identical (``conv1.weight``, ``bn1.running_mean``, ``layer1.0.downsample.0.weigh
 ``fc.bias`` ...), and the same initialisation (kaiming_normal_ fan_out for
 convs, BN weight 1 / bias 0, default Linear init).  ``width`` scales every
 channel count for the small parity fixtures.
+
+Every BatchNorm runs through ``fused_bn.bn_act`` together with the ReLU and the
+residual add that follow it: on an MI355X training step (bf16, channels_last)
+that takes libgsync's fused backward kernels; everywhere else it is the stock
+``relu(bn(x) + identity)``.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
+
+from .fused_bn import bn_act
 
 
 def conv3x3(in_planes, out_planes, stride=1):
@@ -22,6 +29,11 @@ def conv3x3(in_planes, out_planes, stride=1):
 
 def conv1x1(in_planes, out_planes, stride=1):
     return nn.Conv2d(in_planes, out_planes, kernel_size=1, stride=stride, bias=False)
+
+
+def _downsample(seq, x):
+    """The block's downsample branch, Sequential(conv1x1, BatchNorm2d): the BN through bn_act."""
+    return bn_act(seq[1], seq[0](x), relu=False)
 
 
 class BasicBlock(nn.Module):
@@ -39,12 +51,10 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.bn2(self.conv2(out))
         if self.downsample is not None:
-            identity = self.downsample(x)
-        out += identity
-        return self.relu(out)
+            identity = _downsample(self.downsample, x)
+        out = bn_act(self.bn1, self.conv1(x))
+        return bn_act(self.bn2, self.conv2(out), residual=identity)
 
 
 class Bottleneck(nn.Module):
@@ -64,13 +74,11 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
         if self.downsample is not None:
-            identity = self.downsample(x)
-        out += identity
-        return self.relu(out)
+            identity = _downsample(self.downsample, x)
+        out = bn_act(self.bn1, self.conv1(x))
+        out = bn_act(self.bn2, self.conv2(out))
+        return bn_act(self.bn3, self.conv3(out), residual=identity)
 
 
 class ResNet(nn.Module):
@@ -108,7 +116,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.maxpool(bn_act(self.bn1, self.conv1(x)))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = torch.flatten(self.avgpool(x), 1)
         return self.fc(x)

@@ -661,6 +661,40 @@ int gs_image_augment(int device_kind, int device, const uint8_t* src, const int6
                      int H, int W, int C, int pad, int out_h, int out_w, const int32_t* params, int64_t B,
                      void* out, int out_dtype, int out_layout, int64_t* out_labels, void* stream);
 
+/* ======================================================================
+ * NHWC BatchNorm backward fused with the ReLU mask and the residual add
+ * (csrc/gs_bn_kernels.hip; autograd glue: distributed_training_amd/fused_bn.py)
+ * replaces: miopen_batch_norm_backward + threshold_backward (+ the in-place
+ *           add and ReLU of the block's tail in the forward)
+ *
+ * An activation is a row-major [R, C] bf16 matrix (R = N*H*W, NHWC), C % 8 == 0,
+ * every pointer 16-byte aligned; mean / invstd / weight / grad_* are fp32 [C].
+ * HIP only: each entry launches on `stream` of the current device, allocates
+ * nothing and never synchronises, so it can be recorded into a hipGraph.
+ * Results are deterministic: fixed reduction order, no float atomics.
+ * ==================================================================== */
+/* P, the number of per-workgroup partial sums of (R, C): the workspace both
+ * backward entries take holds P * C * 2 floats ([P, C, 2]) */
+int gs_bn_bwd_partials(int64_t R, int C);
+/* partial sums of g and g * (x - mean) per channel into ws, with
+ * g = dy * [y > 0] (y != NULL) or dy (xhat = (x - mean) * invstd: the dx
+ * pass scales the folded sum by invstd once).
+ * g_out != NULL: g is also written as bf16 (bit-identical to
+ * threshold_backward(dy, y, 0)), the gradient of a residual branch. */
+int gs_bn_bwd_reduce(const void* x, const void* dy, const void* y, void* g_out, const float* mean, float* ws,
+                     int64_t ws_floats, int64_t R, int C, void* stream);
+/* folds the partials in index order and writes
+ * dx = weight * invstd * (g - sum(g)/R - xhat * sum(g*xhat)/R) as bf16
+ * (truncated, as the MIOpen kernels it replaces convert it),
+ * grad_weight = sum(g*xhat), grad_bias = sum(g); g = dy * [y > 0] (y != NULL) or dy */
+int gs_bn_bwd_dx(const void* x, const void* dy, const void* y, const float* mean, const float* invstd,
+                 const float* weight, const float* ws, int64_t ws_floats, void* dx, float* grad_weight,
+                 float* grad_bias, int64_t R, int C, void* stream);
+/* t = relu(t + identity) in place over n bf16 elements (n % 8 == 0): the sum
+ * formed in fp32 and rounded once to bf16, then max with 0; bit-identical to
+ * ATen's add_ followed by relu_ */
+int gs_add_relu_fwd(void* t, const void* identity, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
