@@ -19,6 +19,9 @@ row also `batched_*`: the same launches back to back between one event pair):
   LAMB moments        24 B/param    (p, g, m, v read; m, v written; per-tensor sums of p^2, u^2)
   LAMB update         16 B/param    (timed in-step, right behind its moments pass)
   LAMB step           40 B/param    foreach lerp_ / mul_ / addcmul_ / sqrt / div / add + the two norms + ratios + add_
+  EMA fp32            12 B/param    torch._foreach_lerp_ (AveragedModel.update_parameters)
+  EMA + bf16 copy     14 B/param    (fp32 shadow of a bf16 model, the copy written in the same pass)
+  EMA bf16 source     10 B/param
 
 Working sets are replicated `--replicas` times so the timed data exceeds the
 256 MiB Infinity Cache (true HBM rates).  Prints one JSON object per kernel.
@@ -223,6 +226,33 @@ def main():
             ratio_to_plain=upd16[0] / upd[0], byte_ratio=18 / 16)
         both = timeit(lamb_step, args.iters)  # one event pair around the two launches
         rec("lamb_step", 40 * n, *both, "libgsync")
+    # EMA / SWA weight averaging (gs_ema_step, as AveragedModel launches it): the average against
+    # the fp32 parameters, the same with the bf16 copy of the new average, and a bf16 source;
+    # torch's path for the same work is _foreach_lerp_
+    if want("ema"):
+        numels = [torch.Size(s).numel() for s in shapes]
+        eplan = TensorListPlan(numels, dev, task_units=update_task_units(dev))
+        avg = [p.clone() for p in params]
+        src16 = [p.bfloat16() for p in params]
+        avg16 = [torch.zeros(s, device=dev, dtype=torch.bfloat16) for s in shapes]
+        eplan.set_ptrs(0, avg)
+        eplan.set_ptrs(1, params)
+        eplan.set_ptrs(2, avg16)
+        rec("ema_f32", 12 * n, *timeit_plan(eplan, lambda: eplan.ema(torch.float32, 1e-4), args.iters,
+                                            kind=L.GS_OP_EMA), "libgsync")
+        rec("ema_f32_copy_bf16", 14 * n, *timeit_plan(
+            eplan, lambda: eplan.ema(torch.float32, 1e-4, lowp_dtype=torch.bfloat16), args.iters, kind=L.GS_OP_EMA),
+            "libgsync")
+        eplan.set_ptrs(1, src16)
+        rec("ema_bf16src", 10 * n, *timeit_plan(eplan, lambda: eplan.ema(torch.bfloat16, 1e-4), args.iters,
+                                                kind=L.GS_OP_EMA), "libgsync")
+        if not args.skip_torch:
+            tavg = [p.clone() for p in params]
+            rec("ema_f32", 12 * n, *timeit(lambda: torch._foreach_lerp_(tavg, params, 1e-4), args.iters),
+                "torch _foreach_lerp_")
+            del tavg
+        eplan.close()
+        del avg, src16, avg16
     if not args.skip_torch and want("lamb"):
         # a LAMB step of the same arithmetic as torch foreach ops, everything on the device
         bp, bm, bv = [p.clone() for p in params], [x.clone() for x in ms], [x.clone() for x in vs]

@@ -42,6 +42,8 @@ GS_LAYOUT_NCHW, GS_LAYOUT_NHWC = 0, 1
 GS_OP_PACK, GS_OP_UNPACK, GS_OP_SCALE, GS_OP_SQNORM, GS_OP_UNSCALE, GS_OP_SGD, GS_OP_ADAM, GS_OP_SUM = 1, 2, 3, 4, 5, 6, 7, 8
 GS_OP_LARS_NORM, GS_OP_LARS = 9, 10
 GS_OP_LAMB_MOMENTS, GS_OP_LAMB = 11, 12
+GS_OP_EMA = 13
+GS_EMA_EMA, GS_EMA_SWA, GS_EMA_WARMUP = 0, 1, 2
 
 _TORCH_TO_GS = {
     torch.float32: GS_F32,
@@ -140,6 +142,8 @@ SIGNATURES = {
     "gs_lamb_moments": (_c_int, [_vp, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp, _vp]),
     "gs_lamb_step": (_c_int, [_vp, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp]),
     "gs_lamb_hyper": (_c_int, [_c_int, _vp, _vp, _c_d, _c_d, _c_int, _vp, _vp, _vp]),
+    "gs_ema_step": (_c_int, [_vp, _c_int, _c_int, _c_d, _c_int, _vp]),
+    "gs_ema_hyper": (_c_int, [_c_int, _vp, _c_int, _c_d, _vp, _vp]),
     "gs_compute_bucket_assignment": (
         _c_int,
         [_c_int, _p_i64, _p_i32, _p_i32, _c_int, _p_i64, _p_i32, _p_i32, _p_i32],

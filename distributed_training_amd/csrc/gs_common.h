@@ -356,6 +356,28 @@ GS_HD inline void lamb_hyper_update(double* step, const double* lr, double beta1
 }
 int hip_adam_hyper(double* step, const double* lr, double beta1, double beta2, double wd,
                    const float* found_inf, float* hyper, void* stream);
+// The averaging weight of gs_ema_step from the device update counter (gs_ema_hyper):
+// hyper = [w, copy flag]; n_averaged advances.  EMA and the warm-up form their weight in
+// double as Python does (1 - decay), SWA with the one fp32 division of 1 / (n + 1) on an
+// int64 tensor.
+GS_HD inline void ema_hyper_update(int64_t* n_averaged, int mode, double decay, float* hyper) {
+  const int64_t n = n_averaged[0];
+  float w;
+  if (mode == GS_EMA_SWA) {
+    w = 1.0f / static_cast<float>(n + 1);
+  } else if (mode == GS_EMA_WARMUP) {
+    const double ramp = (1.0 + static_cast<double>(n)) / (10.0 + static_cast<double>(n));
+    w = static_cast<float>(1.0 - (decay < ramp ? decay : ramp));
+  } else {
+    w = static_cast<float>(1.0 - decay);
+  }
+  hyper[0] = w;
+  hyper[1] = n == 0 ? 1.f : 0.f;
+  n_averaged[0] = n + 1;
+}
+int hip_ema_hyper(int64_t* n_averaged, int mode, double decay, float* hyper, void* stream);
+int hip_ema(gs_plan* p, int sdt, int ldt, float w, int copy, void* stream);
+int host_ema(gs_plan* p, int sdt, int ldt, float w, int copy);
 
 // Deferred watchdog marks (gs_comm.cpp): a consumer plan's launch carries the mark of
 // the collectives deferred to it.  comm_mark_take: 0 = nothing to do (the

@@ -1204,6 +1204,67 @@ struct AdamOp {
   }
 };
 
+// EMA / SWA weight averaging (gs_ema_step): slots 0 = average a (f32), 1 = source s (SD,
+// converted to fp32 on load), 2 = low-precision copy of the new a (LD; LD < 0: no copy, no
+// third stream).  a' = lerp(a, s, w) in torch's CPU form (include/gsync.h): below |w| = 0.5
+// the form AdamOp uses for exp_avg.lerp_, at or above it the form anchored on s.  Copy mode
+// (the first update, and the buffers torch keeps "in sync") moves s: the average is not
+// loaded and no arithmetic touches the value, so with SD = f32 any 32-bit word rides along
+// (int64 buffers as pairs of words, NaN patterns included).  w and the copy flag are
+// wave-uniform: from the arguments or, once per workgroup, from the plan's hyper source
+// [w, copy] (gs_ema_hyper writes it), so a captured update follows SWA's 1/(n+1).
+// NTS: non-temporal loads of the source (a read-once stream larger than the Infinity Cache,
+// nt_read_once); the average keeps cached loads, as every read-modify-write stream here.
+template <int N, int SD, int LD = -1, bool NTS = false>
+struct EmaOp {
+  static constexpr int kN = N;
+  static constexpr int kG = GS_G_SGD;
+  static constexpr int kRed = 0;
+  static constexpr int kRedGrid = kGridLimit;
+  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
+  static constexpr int kKind = GS_OP_EMA;
+  float* partials = nullptr;
+  float w;
+  int copy;
+  const float* hyper = nullptr;  // [w, copy flag] in device memory (gs_plan_set_hyper_source)
+  float wm1 = 0.f;               // w - 1 (set by load_hyper)
+  bool high = false;             // |w| >= 0.5 (set by load_hyper)
+  struct Frag { float a[N], s[N]; };
+  __device__ int phys(int k) const { return k; }
+  __device__ bool active() const { return true; }
+  __device__ bool fast_ok(const TV& v) const { return v.vec(0) && v.vec(1) && (LD < 0 || v.vec(2)); }
+  template <bool F>
+  __device__ void load(const TV& v, int64_t e0, uint32_t lo, Frag& f) const {
+    if (!copy) ld<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.a);
+    ld<SD, N, F, NTS>(v.ptr[1], e0, lo, v.numel, v.vec(1), f.s);
+  }
+  template <bool F>
+  __device__ void apply(const TV& v, int64_t e0, uint32_t lo, Frag& f, float&) const {
+    if (copy) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) f.a[i] = f.s[i];
+    } else if (high) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) f.a[i] = fmaf(wm1, f.s[i] - f.a[i], f.s[i]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < N; ++i) f.a[i] = fmaf(w, f.s[i] - f.a[i], f.a[i]);
+    }
+    st<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.a);
+    // the copy is the cast of the stored fp32 value (from_f32 pins it: no fma folded into the cast)
+    if constexpr (LD >= 0) st<LD, N, F>(v.ptr[2], e0, lo, v.numel, v.vec(2), f.a);
+  }
+};
+template <int N, int SD, int LD, bool NTS>
+__device__ __forceinline__ void load_hyper(EmaOp<N, SD, LD, NTS>& op) {
+  if (op.hyper) {
+    op.w = op.hyper[0];
+    op.copy = op.hyper[1] != 0.f;
+  }
+  op.wm1 = op.w - 1.0f;
+  op.high = fabsf(op.w) >= 0.5f;
+}
+
 // The update's grad multiplier, formed once per workgroup (uniform): *gscale
 // (AMP unscale / a precomputed clip coefficient) or, with a folded clip, the
 // clip coefficient itself — from a finished Σg² or from the Σg² kernel's group

@@ -379,6 +379,41 @@ int host_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gsc
   return GS_OK;
 }
 
+// EMA / SWA averaging on the host (include/gsync.h, gs_ema_step): EmaOp's arithmetic with
+// the hardware fmaf.  Copy mode with an fp32 source is a memcpy: no float register sees the
+// words, so integer buffers and NaN patterns pass unchanged.
+int host_ema(gs_plan* p, int sdt, int ldt, float w, int copy) {
+  const float wm1 = w - 1.0f;
+  const bool high = std::fabs(w) >= 0.5f;
+  GS_HOST_FLOAT(sdt, SD, GS_HOST_LOWP(ldt, LD, {
+    for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
+      float* ap = static_cast<float*>(slot(p, 0, t));
+      const void* sp = slot(p, 1, t);
+      void* lp = slot(p, 2, t);
+      if (copy) {
+        if constexpr (SD == GS_F32) {
+          std::memcpy(ap + i0, static_cast<const float*>(sp) + i0, sizeof(float) * static_cast<size_t>(i1 - i0));
+        } else {
+          for (int64_t i = i0; i < i1; ++i) ap[i] = ldT<SD>(sp, i);
+        }
+      } else if (high) {
+        for (int64_t i = i0; i < i1; ++i) {
+          const float s = ldT<SD>(sp, i);
+          ap[i] = std::fmaf(wm1, s - ap[i], s);
+        }
+      } else {
+        for (int64_t i = i0; i < i1; ++i) {
+          const float s = ldT<SD>(sp, i);
+          ap[i] = std::fmaf(w, s - ap[i], ap[i]);
+        }
+      }
+      if constexpr (LD >= 0)
+        for (int64_t i = i0; i < i1; ++i) stT<LD>(lp, i, ap[i]);
+    });
+  }));
+  return GS_OK;
+}
+
 // LARS on the host (include/gsync.h, gs_lars_step): the same contract as the device
 // kernels — fp32, every multiply and add rounded once, no fma.  The per-tensor sums
 // run in element order, 1 Ki-element blocks folded front to back: a fixed order

@@ -695,6 +695,39 @@ int gs_lamb_hyper(int device_kind, double* step, const double* lr, double beta1,
   return hip_lamb_hyper(step, lr, beta1, beta2, bias_correction, found_inf, hyper, stream);
 }
 
+int gs_ema_step(gs_plan* p, int src_dtype, int lowp_dtype, double weight, int copy, void* stream) {
+  GsRange range("gs_ema_step");
+  PLAN_OK(p);
+  GS_CHECK_ARG(is_float_dtype(src_dtype), "gs_ema_step: source dtype must be f32, bf16 or f16");
+  GS_CHECK_ARG(weight >= 0.0 && weight <= 1.0, "gs_ema_step: weight must be in [0, 1]");
+  if (p->clip_on)
+    return fail(GS_ESTATE, "gs_ema_step: a gradient-norm clip is set on the plan (gs_plan_set_clip); "
+                           "averaging has no gradients to clip");
+  GS_TRY_RET(lars_slots_bound(p, 2, "gs_ema_step"));
+  GS_TRY_RET(lowp_slot_ok(p, lowp_dtype, 2, "gs_ema_step"));
+  float w = static_cast<float>(weight);
+  int cp = copy != 0;
+  if (p->kind == GS_DEV_HOST) {
+    if (p->hyper) {
+      w = p->hyper[0];
+      cp = p->hyper[1] != 0.f;
+    }
+    return host_ema(p, src_dtype, lowp_dtype, w, cp);
+  }
+  return hip_ema(p, src_dtype, lowp_dtype, w, cp, stream);
+}
+
+int gs_ema_hyper(int device_kind, int64_t* n_averaged, int mode, double decay, float* hyper, void* stream) {
+  GS_CHECK_ARG(n_averaged && hyper, "gs_ema_hyper: NULL argument");
+  GS_CHECK_ARG(mode == GS_EMA_EMA || mode == GS_EMA_SWA || mode == GS_EMA_WARMUP, "gs_ema_hyper: unknown mode");
+  GS_CHECK_ARG(decay >= 0.0 && decay <= 1.0, "gs_ema_hyper: decay must be in [0, 1]");
+  if (device_kind == GS_DEV_HOST) {
+    ema_hyper_update(n_averaged, mode, decay, hyper);
+    return GS_OK;
+  }
+  return hip_ema_hyper(n_averaged, mode, decay, hyper, stream);
+}
+
 int gs_plan_set_hyper_source(gs_plan* p, const float* hyper) {
   PLAN_OK(p);
   p->hyper = hyper;

@@ -2,7 +2,8 @@
 // gs_lars_step[_lowp]): the chunk-map engine of gs_engine.h with SgdOp / AdamOp / LarsOp, the
 // grad-load policy per launch; LARS's per-tensor Σp², Σg² (gs_lars_norms), a segmented
 // reduction over the same chunk map; and LAMB (gs_lamb_moments / gs_lamb_step): that
-// reduction fused with the moments' read-modify-write, then LambOp on the engine.
+// reduction fused with the moments' read-modify-write, then LambOp on the engine; and the
+// EMA / SWA weight average (gs_ema_step / gs_ema_hyper): EmaOp on the engine.
 
 #include "gs_engine.h"
 
@@ -53,6 +54,37 @@ int hip_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gsc,
   DeviceGuard g(p->device);
   return nt_grad(p, gdt) ? adam_nt<true>(p, gdt, ldt, h, gsc, fi, clip, stream)
                          : adam_nt<false>(p, gdt, ldt, h, gsc, fi, clip, stream);
+}
+
+// -------------------------------------------------------------------- EMA
+// gs_ema_step: EmaOp on the engine, one instantiation per (source dtype, copy dtype).  The
+// average takes cached loads (a read-modify-write stream); the source, read once by this
+// launch, follows the engine's size rule (nt_read_once): non-temporal above the Infinity Cache.
+template <bool NTS>
+static int ema_nt(gs_plan* p, int sdt, int ldt, float w, int copy, void* stream) {
+  GS_DISPATCH_FLOAT(sdt, SD, GS_DISPATCH_LOWP(ldt, LD, {
+    EmaOp<kUnit, SD, LD, NTS> op;
+    op.w = w; op.copy = copy; op.hyper = p->hyper;
+    return launch(p, op, stream);
+  }));
+  return GS_OK;
+}
+
+int hip_ema(gs_plan* p, int sdt, int ldt, float w, int copy, void* stream) {
+  DeviceGuard g(p->device);
+  return nt_read_once(p->elems * dtype_bytes(sdt)) ? ema_nt<true>(p, sdt, ldt, w, copy, stream)
+                                                   : ema_nt<false>(p, sdt, ldt, w, copy, stream);
+}
+
+__global__ void ema_hyper_kernel(int64_t* n_averaged, int mode, double decay, float* hyper) {
+  if (threadIdx.x == 0) ema_hyper_update(n_averaged, mode, decay, hyper);
+}
+
+int hip_ema_hyper(int64_t* n_averaged, int mode, double decay, float* hyper, void* stream) {
+  hipLaunchKernelGGL(ema_hyper_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), n_averaged, mode,
+                     decay, hyper);
+  HIP_RET(hipGetLastError());
+  return GS_OK;
 }
 
 // ------------------------------------------------------------------- LARS

@@ -346,6 +346,19 @@ class TensorListPlan:
             "gs_lamb_step",
         )
 
+    # ------------------------------------------------------------------- EMA
+    def ema(self, src_dtype, weight=0.0, copy=False, lowp_dtype=None, stream=None):
+        """The weight average on slots 0 = average (fp32), 1 = source (``src_dtype``):
+        a = lerp(a, s, weight) in torch.lerp's CPU form, or a = s when ``copy``; with
+        ``lowp_dtype`` (bf16 / fp16) it also writes slot 2 = that copy of the new a
+        (gs_ema_step).  With a hyper source on the plan ([weight, copy flag],
+        :func:`ema_hyper`) both are read from it when the kernel runs."""
+        L.check(
+            L.lib().gs_ema_step(self.handle, L.gs_dtype(src_dtype), -1 if lowp_dtype is None else L.gs_dtype(lowp_dtype),
+                                float(weight), int(bool(copy)), self._stream(stream)),
+            "gs_ema_step",
+        )
+
     def adam(self, grad_dtype, lr, beta1, beta2, eps, weight_decay, adamw, maximize, step_size,
              bias_correction2_sqrt, lowp_dtype=None, grad_scale=None, found_inf=None, stream=None):
         L.check(
@@ -369,6 +382,21 @@ def clip_coef(sqnorm: torch.Tensor, max_norm: float, eps: float, coef: torch.Ten
                              None if norm is None else norm.data_ptr(), stream),
         "gs_clip_coef",
     )
+
+
+def ema_hyper(n_averaged: torch.Tensor, mode: int, decay: float, hyper: torch.Tensor, stream=None):
+    """hyper[:2] = [averaging weight, first-update flag] from the int64 counter
+    ``n_averaged``, which advances (gs_ema_hyper; one thread on the stream, capturable).
+    ``mode``: L.GS_EMA_EMA / GS_EMA_SWA / GS_EMA_WARMUP."""
+    if n_averaged.dtype != torch.int64 or n_averaged.numel() != 1:
+        raise ValueError("n_averaged: an int64 scalar")
+    if hyper.dtype != torch.float32 or hyper.numel() < 2 or not hyper.is_contiguous() or \
+            hyper.device != n_averaged.device:
+        raise ValueError("hyper: contiguous fp32[>= 2] beside n_averaged")
+    if stream is None:
+        stream = L.stream_ptr(hyper.device)
+    L.check(L.lib().gs_ema_hyper(L.device_kind(hyper), n_averaged.data_ptr(), int(mode), float(decay),
+                                 hyper.data_ptr(), stream), "gs_ema_hyper")
 
 
 def is_dense(t: torch.Tensor) -> bool:

@@ -766,9 +766,16 @@ class ZeroDataParallel:
         (DeepSpeed ``zero_to_fp32`` / ``get_fp32_state_dict_from_zero_checkpoint``;
         Colossal ``save_model(shard=False)``).  Collective: every rank calls it
         and every rank gets it.  Buffers are this rank's."""
+        return self._consolidate(self.master)
+
+    @torch.no_grad()
+    def _consolidate(self, shards, buffers=None) -> dict:
+        """The gather behind :meth:`consolidated_state_dict` for any per-bucket fp32
+        shards laid out as ``master`` (the weight average's too, ema.py); ``buffers``
+        replaces the module's buffers by name."""
         self.wait_allgather()
         fulls = []
-        for b, m in enumerate(self.master):
+        for b, m in enumerate(shards):
             full = torch.empty(self.bucket_numel[b], dtype=torch.float32, device=self.device)
             if self._comm is not None:
                 self._comm.all_gather(m.contiguous(), full, stream=L.stream_ptr(self.device))
@@ -787,6 +794,8 @@ class ZeroDataParallel:
         names = {id(p): n for n, p in self.module.named_parameters()}
         pn = {names[id(p)]: id(p) for p in self.params}
         for k, v in self.module.state_dict().items():
+            if k not in pn and buffers is not None and k in buffers:
+                v = buffers[k]
             out[k] = by_id[pn[k]].detach().cpu().clone() if k in pn else v.detach().cpu().clone()
         return out
 

@@ -208,6 +208,7 @@ int64_t gs_plan_task_units(gs_plan* p);
 #define GS_OP_LARS 10
 #define GS_OP_LAMB_MOMENTS 11 /* gs_lamb_moments: the chunk pass and its fold, one record */
 #define GS_OP_LAMB 12
+#define GS_OP_EMA 13
 int gs_plan_timer_enable(gs_plan* p, int n_slots);
 int gs_plan_timer_read(gs_plan* p, float* ms_out, int32_t* kind_out, int cap);
 /* register the per-tensor pointers of one slot (uploads on change, ordered on `stream`) */
@@ -424,6 +425,7 @@ int gs_lars_step_lowp(gs_plan* p, int grad_dtype, int lowp_dtype, double lr, dou
  *         hyper[2] = 1 - lr*wd (AdamW decay)
  *   LARS: hyper[0] = lr
  *   LAMB: hyper[0] = lr, hyper[1] = bc1, hyper[2] = bc2_sqrt (gs_lamb_hyper)
+ *   EMA:  hyper[0] = w, hyper[1] != 0 = copy mode (gs_ema_hyper)
  * (fp32, device memory for HIP plans, host memory for host plans) when the
  * kernel runs, so a step recorded into a hipGraph follows an LR schedule and
  * Adam's bias corrections on replay; the argument values are then ignored.
@@ -508,6 +510,48 @@ int gs_lamb_step_lowp(gs_plan* p, int lowp_dtype, double lr, double eps, double 
  * replaces: the host-side `state["step"] += 1` and bias corrections of a Python LAMB */
 int gs_lamb_hyper(int device_kind, double* step, const double* lr, double beta1, double beta2, int bias_correction,
                   const float* found_inf, float* hyper, void* stream);
+
+/* EMA / SWA weight averaging: one pass a' = lerp(a, s, w) over a whole model.
+ * Slots: 0 = the average a (f32), 1 = the source s (src_dtype: f32, bf16 or f16, converted
+ * to fp32 on load), 2 = a low-precision copy of the new a (lowp_dtype GS_BF16 / GS_F16;
+ * -1 = none, and then slot 2 is not touched).  12 B/param with an fp32 source (reads 8,
+ * writes 4), 10 with a 16-bit one, + 2 with the copy.
+ * Arithmetic (all fp32; w = the weight rounded to fp32), the same on both backends:
+ *   copy mode:    a' = s                         (bits moved; no arithmetic touches the value)
+ *   |w| <  0.5:   a' = fmaf(w, s - a, a)
+ *   |w| >= 0.5:   a' = fmaf(w - 1.0f, s - a, s)  (w - 1.0f one fp32 subtraction)
+ *   lowp copy:    cast(a'), round to nearest even of the STORED fp32 a'
+ * which is torch.lerp's CPU kernel bit for bit on either side of the 0.5 switch.  In copy
+ * mode with an fp32 source any 32-bit word is moved unchanged, so an int64 tensor can ride
+ * along as 2*numel fp32 words (NaN-patterned halves are not quieted); a 16-bit source is
+ * converted (bf16 exactly).
+ * With a hyper source on the plan (gs_plan_set_hyper_source) the kernel reads
+ * hyper[0] = w and hyper[1] != 0 = copy mode when it runs (gs_ema_hyper writes both), and
+ * the weight / copy arguments are ignored (the weight is still range-checked).
+ * GS_EINVAL before any launch: a dtype outside the lists above, a weight outside [0, 1] or
+ * NaN, an unbound slot of a non-empty tensor.  A clip set on the plan is GS_ESTATE.
+ * replaces: T:optim/swa_utils.py AveragedModel.update_parameters (the per-parameter copy_
+ *           of the first update, torch._foreach_lerp_ of the later ones, the per-buffer
+ *           copy_ that keeps buffers in sync), get_ema_multi_avg_fn, get_swa_multi_avg_fn */
+int gs_ema_step(gs_plan* p, int src_dtype, int lowp_dtype /* -1 none */, double weight, int copy,
+                void* stream);
+/* The averaging weight from the device-side update counter (one thread; graph-capturable),
+ * gs_adam_hyper's counterpart:
+ *   n = *n_averaged;  hyper[1] = (n == 0)                       (the first update copies)
+ *   GS_EMA_EMA:     hyper[0] = (float)(1 - decay)               (the difference in double)
+ *   GS_EMA_SWA:     hyper[0] = 1.0f / (float)(n + 1)            (one fp32 division)
+ *   GS_EMA_WARMUP:  hyper[0] = (float)(1 - min(decay, (1 + n) / (10 + n)))   (in double)
+ *   *n_averaged = n + 1
+ * n_averaged: int64 scalar, hyper: fp32[>= 2], both where device_kind says.  GS_EMA_SWA
+ * does not use decay (pass 0).  GS_EINVAL: NULL pointers, an unknown mode, decay outside [0, 1].
+ * replaces: T:optim/swa_utils.py AveragedModel.update_parameters (`bool(n_averaged == 0)`,
+ *           `n_averaged > 0`, `n_averaged += 1`), get_ema_multi_avg_fn (1 - decay),
+ *           get_swa_multi_avg_fn (1 / (num_averaged + 1)) */
+#define GS_EMA_EMA 0
+#define GS_EMA_SWA 1
+#define GS_EMA_WARMUP 2
+int gs_ema_hyper(int device_kind, int64_t* n_averaged, int mode, double decay, float* hyper /*[2]*/,
+                 void* stream);
 
 /* ======================================================================
  * bucket assignment (greedy by size per dtype, first-bucket cap)
