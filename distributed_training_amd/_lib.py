@@ -122,8 +122,11 @@ SIGNATURES = {
                                   _vp, _c_i64, _vp, _c_int, _c_int, _vp, _vp]),
     "gs_bn_bwd_partials": (_c_int, [_c_i64, _c_int]),
     "gs_bn_bwd_reduce": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _vp]),
+    "gs_bn_bwd_reduce_fork": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _vp]),
     "gs_bn_bwd_dx": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_int, _vp]),
     "gs_add_relu_fwd": (_c_int, [_vp, _vp, _c_i64, _vp]),
+    "gs_relu_maxpool_fwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
+    "gs_maxpool_bwd": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
     "gs_clip_coef":(_c_int, [_c_int, _vp, _c_f, _c_f, _vp, _vp, _vp]),
     "gs_unscale_check": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),
     "gs_sgd_step": (

@@ -18,6 +18,11 @@
 // the streamed bytes, bounded by bn_geom) - the folded-partials idiom of the
 // clipped update in gs_update_kernels.hip.  No atomics, so the result is
 // deterministic.
+//
+// gs_bn_bwd_reduce_fork is the reduce pass fed the two halves of a fork's gradient
+// (one more stream in, ATen's bf16 add in registers).  The stem's tail has its own
+// pair: relu_maxpool_fwd_kernel (ReLU taken while pooling, a byte per output for
+// the winner) and maxpool_bwd_kernel (dx written once from those bytes).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,6 +60,10 @@ constexpr int kBnTileVecs = 8;         // vectors (of 8 channels) per channel ti
 constexpr int kBnMaxP = 512;           // row-blocks, at most
 constexpr int kBnTargetBlocks = 1024;  // 4 workgroups per CU
 constexpr int kBnUnroll = 4;           // rows in flight per thread and stream
+#ifndef GS_BN_FORK_UNROLL
+#define GS_BN_FORK_UNROLL 4
+#endif
+constexpr int kBnForkUnroll = GS_BN_FORK_UNROLL;  // the same, for the reduce that sums two gradients
 
 // The decomposition of (R, C), the same for both backward kernels.
 //   P <= ceil(R / ty): a row-block has at least one step of rows;
@@ -143,11 +152,22 @@ __device__ __forceinline__ void relu_mask(float (&g)[8], const bu4& yv) {
   for (int i = 0; i < 8; ++i) g[i] = yf[i] <= 0.f ? 0.f : g[i];
 }
 
+// dy = dy_a + dy_b as ATen's bf16 add forms it: the sum in fp32, rounded once to bf16
+__device__ __forceinline__ void fork_sum(float (&g)[8], const bu4& bv) {
+  float b[8];
+  unpack8(bv, b);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) g[i] = __uint_as_float(to_bf16(g[i] + b[i]) << 16);
+}
+
 // ---- pass 1: per-workgroup partial sums of g and g * xhat (and g itself) ----
-template <bool RELU, bool WRITE_G>
+// FORK: the gradient arrives as the two halves of a fork (dy, dy2) and is summed here
+template <bool RELU, bool WRITE_G, bool FORK>
 __global__ void __launch_bounds__(kBlock)
-bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
-                     uint16_t* __restrict__ gout, const float* __restrict__ mean, float* __restrict__ ws, int64_t R, int C, int tx_log2, int64_t rpb) {
+bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, const uint16_t* __restrict__ dy2,
+                     const uint16_t* __restrict__ y, uint16_t* __restrict__ gout, const float* __restrict__ mean,
+                     float* __restrict__ ws, int64_t R, int C, int tx_log2, int64_t rpb) {
+  constexpr int U = FORK ? kBnForkUnroll : kBnUnroll;
   __shared__ float s_red[kBlock * 16];  // [ty][F], F = 16 * tx: (channel, {sum g, sum g*(x-mean)})
   __shared__ double s_grp[kBlock];      // [ty / 16][F]
   const int t = threadIdx.x;
@@ -167,10 +187,11 @@ bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict_
     m[i] = active ? mean[c0 + i] : 0.f;
   }
   // one row's vector: sum g, sum g * (x - mean); invstd scales the second sum once, after the dx pass's fold
-  auto body = [&](const bu4& xv, const bu4& dv, const bu4& yv, int64_t off) {
+  auto body = [&](const bu4& xv, const bu4& dv, const bu4& bv, const bu4& yv, int64_t off) {
     float xf[8], g[8];
     unpack8(xv, xf);
     unpack8(dv, g);
+    if constexpr (FORK) fork_sum(g, bv);
     if constexpr (RELU) relu_mask(g, yv);
     if constexpr (WRITE_G) st16(gout + off, pack8_exact(g));
 #pragma unroll
@@ -183,22 +204,24 @@ bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict_
     const int64_t step = static_cast<int64_t>(ty) * C;
     int64_t r = r0 + ty_i;
     int64_t off = r * C + c0;
-    for (; r + (kBnUnroll - 1) * ty < r1; r += kBnUnroll * ty, off += kBnUnroll * step) {
-      bu4 xv[kBnUnroll], dv[kBnUnroll], yv[kBnUnroll] = {};
+    for (; r + (U - 1) * ty < r1; r += U * ty, off += U * step) {
+      bu4 xv[U], dv[U], bv[U] = {}, yv[U] = {};
 #pragma unroll
-      for (int k = 0; k < kBnUnroll; ++k) {
+      for (int k = 0; k < U; ++k) {
         xv[k] = ld16<false>(x + off + k * step);  // read again by the dx pass
         dv[k] = ld16<GS_BN_NT && WRITE_G>(dy + off + k * step);
+        if constexpr (FORK) bv[k] = ld16<GS_BN_NT>(dy2 + off + k * step);
         if constexpr (RELU) yv[k] = ld16<GS_BN_NT && WRITE_G>(y + off + k * step);
       }
 #pragma unroll
-      for (int k = 0; k < kBnUnroll; ++k) body(xv[k], dv[k], yv[k], off + k * step);
+      for (int k = 0; k < U; ++k) body(xv[k], dv[k], bv[k], yv[k], off + k * step);
     }
     for (; r < r1; r += ty, off += step) {
-      bu4 yv = {0u, 0u, 0u, 0u};
+      bu4 bv = {0u, 0u, 0u, 0u}, yv = {0u, 0u, 0u, 0u};
       const bu4 xv = ld16<false>(x + off), dv = ld16<false>(dy + off);
+      if constexpr (FORK) bv = ld16<false>(dy2 + off);
       if constexpr (RELU) yv = ld16<false>(y + off);
-      body(xv, dv, yv, off);
+      body(xv, dv, bv, yv, off);
     }
   }
   // fold over the ty rows of the workgroup in a fixed order: 16 rows per thread, then the groups.
@@ -348,6 +371,158 @@ add_relu_fwd_kernel(uint16_t* __restrict__ t, const uint16_t* __restrict__ id, i
   }
 }
 
+// ---- the stem: ReLU + MaxPool2d(3, 2, 1) forward, and the pool's backward ----
+// NHWC bf16, a thread owns 8 channels of one pixel (C = 64: one 128-B line per pixel, 8 threads).
+// Window of output (oh, ow): rows 2 oh - 1 .. 2 oh + 1, columns 2 ow - 1 .. 2 ow + 1, clipped.
+
+// relu_ (= clamp_min_(0)): a NaN stays, everything not above 0 (-0 too) becomes +0
+__device__ __forceinline__ float relu1(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
+
+// pooled = max over the window of relu(y), idx = the winner's position 3 * kh + kw in the unclipped
+// window.  Scanned rows outer, columns inner; a later value wins only if it is > the current one or
+// is NaN (ATen's max_pool_forward_nhwc): ties keep the first, the last NaN of the window wins.
+__global__ void __launch_bounds__(kBlock)
+relu_maxpool_fwd_kernel(const uint16_t* __restrict__ y, uint16_t* __restrict__ pooled, uint8_t* __restrict__ idx,
+                        int64_t nvec, int H, int W, int OH, int OW, int V) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= nvec) return;
+  const int cv = static_cast<int>(i % V);
+  int64_t p = i / V;
+  const int ow = static_cast<int>(p % OW);
+  p /= OW;
+  const int oh = static_cast<int>(p % OH);
+  const int64_t n = p / OH;
+  const int h0 = 2 * oh - 1, w0 = 2 * ow - 1;
+  const int64_t C = static_cast<int64_t>(V) * 8;
+  bu4 in[9];
+  bool ok[9];
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh) {
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      const int ih = h0 + kh, iw = w0 + kw, k = 3 * kh + kw;
+      ok[k] = ih >= 0 && ih < H && iw >= 0 && iw < W;
+      in[k] = bu4{0u, 0u, 0u, 0u};
+      if (ok[k]) in[k] = ld16<false>(y + ((n * H + ih) * W + iw) * C + cv * 8);
+    }
+  }
+  float best[8];
+  uint32_t code[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    best[j] = -INFINITY;
+    code[j] = 0;
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    float f[8];
+    unpack8(in[k], f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = relu1(f[j]);
+      const bool take = ok[k] && (v > best[j] || v != v);  // relu(v) >= 0 > -inf: the first valid one is taken
+      best[j] = take ? v : best[j];
+      code[j] = take ? static_cast<uint32_t>(k) : code[j];
+    }
+  }
+  st16(pooled + i * 8, pack8_exact(best));
+  uint2 c;
+  c.x = code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24);
+  c.y = code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24);
+  *reinterpret_cast<uint2*>(idx + i * 8) = c;
+}
+
+// dx of the pool for every input element: the gradients of the (at most 4) windows that contain it and
+// name it their winner, windows visited rows outer, columns inner, ascending; added in fp32 from +0 and
+// rounded once to bf16.  An element inside a single window takes that window's gradient as it is (a -0
+// stays -0), as ATen's max_pool_backward_nhwc does; a 1 x 1 image is NCHW-contiguous as well, ATen runs
+// its NCHW kernel on it, and that one adds to +0.  FORK: a window's gradient is bf16(dA + dB).
+// A thread owns 8 channels of the 2 x 2 input pixels (2a + dh, 2b + dw): the windows that contain them are
+// (a + al, b + be), al <= dh, be <= dw, where pixel (dh, dw) sits at position 3 (dh + 1 - 2 al) + (dw + 1 - 2 be);
+// the four windows' bytes and gradients are read once for the four pixels.
+template <bool FORK>
+__global__ void __launch_bounds__(kBlock)
+maxpool_bwd_kernel(const uint16_t* __restrict__ da, const uint16_t* __restrict__ db, const uint8_t* __restrict__ idx,
+                   uint16_t* __restrict__ dx, int64_t nquad, int H, int W, int OH, int OW, int V) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= nquad) return;  // the quads are as many as the windows: (H + 1) / 2 = OH, (W + 1) / 2 = OW
+  const int cv = static_cast<int>(i % V);
+  int64_t p = i / V;
+  const int b = static_cast<int>(p % OW);
+  p /= OW;
+  const int a = static_cast<int>(p % OH);
+  const int64_t n = p / OH;
+  const bool more_h = a + 1 < OH, more_w = b + 1 < OW;
+  uint2 cw[4];
+  int64_t ovec[4];
+  bool ok[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int al = k >> 1, be = k & 1;
+    ok[k] = (al == 0 || more_h) && (be == 0 || more_w);
+    ovec[k] = ((n * OH + a + al) * OW + b + be) * V + cv;
+    cw[k] = uint2{0xffffffffu, 0xffffffffu};  // no position is 255
+    if (ok[k]) cw[k] = *reinterpret_cast<const uint2*>(idx + ovec[k] * 8);
+  }
+  // a byte of w equal to c?  (a zero byte of w ^ cccc)
+  auto has = [](const uint2& w, uint32_t c) {
+    const uint32_t x0 = w.x ^ (c * 0x01010101u), x1 = w.y ^ (c * 0x01010101u);
+    return ((((x0 - 0x01010101u) & ~x0) | ((x1 - 0x01010101u) & ~x1)) & 0x80808080u) != 0;
+  };
+  bool hit[4];
+  hit[0] = true;  // positions 4, 5, 7, 8 of window (a, b): nearly always one of the 8 channels
+  hit[1] = ok[1] && (has(cw[1], 3u) || has(cw[1], 6u));
+  hit[2] = ok[2] && (has(cw[2], 1u) || has(cw[2], 2u));
+  hit[3] = ok[3] && has(cw[3], 0u);
+  bu4 av[4], bv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    av[k] = bv[k] = bu4{0u, 0u, 0u, 0u};
+    if (hit[k]) {
+      av[k] = ld16<false>(da + ovec[k] * 8);
+      if constexpr (FORK) bv[k] = ld16<false>(db + ovec[k] * 8);
+    }
+  }
+  const bool many = H * W > 1;
+  float acc[4][8];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[q][j] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int al = k >> 1, be = k & 1;
+    float g[8];
+    unpack8(av[k], g);
+    if constexpr (FORK) fork_sum(g, bv[k]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int dh = q >> 1, dw = q & 1;
+      if (dh < al || dw < be) continue;  // compile-time: the window does not contain the pixel
+      const uint32_t want = static_cast<uint32_t>(3 * (dh + 1 - 2 * al) + (dw + 1 - 2 * be));
+      // the pixel's windows: 1 + [dh and a row of windows below] times 1 + [dw and a column to the right]
+      const bool single = many && !(dh == 1 && more_h) && !(dw == 1 && more_w);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t cj = ((j < 4 ? cw[k].x : cw[k].y) >> (8 * (j & 3))) & 0xffu;
+        const bool m = hit[k] && cj == want;
+        acc[q][j] = m ? (single ? g[j] : acc[q][j] + g[j]) : acc[q][j];
+      }
+    }
+  }
+  const int64_t C = static_cast<int64_t>(V) * 8;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int ih = 2 * a + (q >> 1), iw = 2 * b + (q & 1);
+    if (ih < H && iw < W) {
+      bu4 out;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) out[r] = to_bf16(acc[q][2 * r]) | (to_bf16(acc[q][2 * r + 1]) << 16);
+      st16(dx + ((n * H + ih) * W + iw) * C + cv * 8, out);
+    }
+  }
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int check_shape(int64_t R, int C) {
@@ -366,32 +541,84 @@ extern "C" int gs_bn_bwd_partials(int64_t R, int C) {
   return bn_geom(R, C).P;
 }
 
-extern "C" int gs_bn_bwd_reduce(const void* x, const void* dy, const void* y, void* g_out, const float* mean,
-                                float* ws, int64_t ws_floats, int64_t R, int C, void* stream) {
+namespace gs {
+namespace {
+
+// [p, p + pbytes) and [q, q + qbytes) share a byte (a null pointer overlaps nothing)
+bool overlap(const void* p, int64_t pbytes, const void* q, int64_t qbytes) {
+  if (!p || !q) return false;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + static_cast<uintptr_t>(qbytes) && b < a + static_cast<uintptr_t>(pbytes);
+}
+bool overlap(const void* p, const void* q, int64_t bytes) { return overlap(p, bytes, q, bytes); }
+
+// MaxPool2d(3, 2, 1) over [N, H, W, C]: the output's height and width, and the shape checks of both entries
+struct PoolGeom {
+  int OH, OW;
+  int64_t in_vecs, out_vecs;  // vectors of 8 channels
+};
+
+int pool_geom(const std::string& w, int64_t N, int H, int W, int C, PoolGeom* g) {
+  GS_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, w + ": N, H, W, C > 0 and C % 8 == 0 required");
+  GS_CHECK_ARG(N <= ((INT64_MAX / 4) / C / H) / W, w + ": N * H * W * C too large");
+  g->OH = (H - 1) / 2 + 1;
+  g->OW = (W - 1) / 2 + 1;
+  g->in_vecs = N * H * W * (C / 8);
+  g->out_vecs = N * g->OH * g->OW * (C / 8);
+  GS_CHECK_ARG((g->in_vecs + kBlock - 1) / kBlock <= INT_MAX, w + ": N * H * W * C too large");
+  return GS_OK;
+}
+
+// dy_b != NULL: the fork form (g_out required); the checks of both entries
+int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, const void* y, void* g_out,
+              const float* mean, float* ws, int64_t ws_floats, int64_t R, int C, void* stream) {
+  const std::string w(who);
   GS_TRY_RET(check_shape(R, C));
-  GS_CHECK_ARG(x && dy && mean && ws, "gs_bn_bwd_reduce: null pointer");
-  GS_CHECK_ARG(!g_out || y, "gs_bn_bwd_reduce: g_out needs y");
-  GS_CHECK_ARG(aligned16(x) && aligned16(dy) && aligned16(y) && aligned16(g_out) && aligned16(ws),
-               "gs_bn_bwd_reduce: pointers must be 16-byte aligned");
+  GS_CHECK_ARG(x && dy && mean && ws, w + ": null pointer");
+  GS_CHECK_ARG(!g_out || y || dy_b, w + ": g_out needs y");
+  GS_CHECK_ARG(!dy_b || g_out, w + ": two gradients need g_out");
+  GS_CHECK_ARG(aligned16(x) && aligned16(dy) && aligned16(dy_b) && aligned16(y) && aligned16(g_out) && aligned16(ws),
+               w + ": pointers must be 16-byte aligned");
+  if (dy_b) {
+    const int64_t bytes = R * C * 2;
+    GS_CHECK_ARG(!overlap(g_out, x, bytes) && !overlap(g_out, dy, bytes) && !overlap(g_out, dy_b, bytes) &&
+                     !overlap(g_out, y, bytes),
+                 w + ": g_out overlaps an input");
+  }
   const BnGeom g = bn_geom(R, C);
-  GS_CHECK_ARG(ws_floats >= static_cast<int64_t>(g.P) * C * 2, "gs_bn_bwd_reduce: workspace too small");
+  GS_CHECK_ARG(ws_floats >= static_cast<int64_t>(g.P) * C * 2, w + ": workspace too small");
   const dim3 grid(g.ctiles, g.P), block(kBlock);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint16_t* xp = static_cast<const uint16_t*>(x);
   const uint16_t* dp = static_cast<const uint16_t*>(dy);
+  const uint16_t* bp = static_cast<const uint16_t*>(dy_b);
   const uint16_t* yp = static_cast<const uint16_t*>(y);
   uint16_t* gp = static_cast<uint16_t*>(g_out);
-  if (gp)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<true, true>), grid, block, 0, s, xp, dp, yp, gp, mean, ws, R, C,
-                       g.tx_log2, g.rpb);
-  else if (yp)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<true, false>), grid, block, 0, s, xp, dp, yp, gp, mean, ws, R, C,
-                       g.tx_log2, g.rpb);
-  else
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<false, false>), grid, block, 0, s, xp, dp, yp, gp, mean, ws, R, C,
-                       g.tx_log2, g.rpb);
+#define GS_BN_REDUCE(RELU, WRITE_G, FORK)                                                                        \
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<RELU, WRITE_G, FORK>), grid, block, 0, s, xp, dp, bp, yp, gp, mean, ws, R, \
+                     C, g.tx_log2, g.rpb)
+  if (bp && yp) GS_BN_REDUCE(true, true, true);
+  else if (bp) GS_BN_REDUCE(false, true, true);
+  else if (gp) GS_BN_REDUCE(true, true, false);
+  else if (yp) GS_BN_REDUCE(true, false, false);
+  else GS_BN_REDUCE(false, false, false);
+#undef GS_BN_REDUCE
   HIP_RET(hipGetLastError());
   return GS_OK;
+}
+
+}  // namespace
+}  // namespace gs
+
+extern "C" int gs_bn_bwd_reduce(const void* x, const void* dy, const void* y, void* g_out, const float* mean,
+                                float* ws, int64_t ws_floats, int64_t R, int C, void* stream) {
+  return bn_reduce("gs_bn_bwd_reduce", x, dy, nullptr, y, g_out, mean, ws, ws_floats, R, C, stream);
+}
+
+extern "C" int gs_bn_bwd_reduce_fork(const void* x, const void* dy_a, const void* dy_b, const void* y, void* g_out,
+                                     const float* mean, float* ws, int64_t ws_floats, int64_t R, int C,
+                                     void* stream) {
+  return bn_reduce("gs_bn_bwd_reduce_fork", x, dy_a, dy_b, y, g_out, mean, ws, ws_floats, R, C, stream);
 }
 
 extern "C" int gs_bn_bwd_dx(const void* x, const void* dy, const void* y, const float* mean, const float* invstd,
@@ -430,6 +657,51 @@ extern "C" int gs_add_relu_fwd(void* t, const void* identity, int64_t n, void* s
   hipLaunchKernelGGL(add_relu_fwd_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
                      static_cast<hipStream_t>(stream), static_cast<uint16_t*>(t),
                      static_cast<const uint16_t*>(identity), nvec);
+  HIP_RET(hipGetLastError());
+  return GS_OK;
+}
+
+extern "C" int gs_relu_maxpool_fwd(const void* y, void* pooled, void* idx, int64_t N, int H, int W, int C,
+                                   void* stream) {
+  const std::string w("gs_relu_maxpool_fwd");
+  PoolGeom g;
+  GS_TRY_RET(pool_geom(w, N, H, W, C, &g));
+  GS_CHECK_ARG(y && pooled && idx, w + ": null pointer");
+  GS_CHECK_ARG(aligned16(y) && aligned16(pooled) && aligned16(idx), w + ": pointers must be 16-byte aligned");
+  const int64_t ib = g.in_vecs * 16, ob = g.out_vecs * 16, xb = g.out_vecs * 8;
+  GS_CHECK_ARG(!overlap(y, ib, pooled, ob) && !overlap(y, ib, idx, xb) && !overlap(pooled, ob, idx, xb),
+               w + ": buffers overlap");
+  const unsigned blocks = static_cast<unsigned>((g.out_vecs + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(relu_maxpool_fwd_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const uint16_t*>(y), static_cast<uint16_t*>(pooled), static_cast<uint8_t*>(idx),
+                     g.out_vecs, H, W, g.OH, g.OW, C / 8);
+  HIP_RET(hipGetLastError());
+  return GS_OK;
+}
+
+extern "C" int gs_maxpool_bwd(const void* d_a, const void* d_b, const void* idx, void* dx, int64_t N, int H, int W,
+                              int C, void* stream) {
+  const std::string w("gs_maxpool_bwd");
+  PoolGeom g;
+  GS_TRY_RET(pool_geom(w, N, H, W, C, &g));
+  GS_CHECK_ARG(d_a && idx && dx, w + ": null pointer");
+  GS_CHECK_ARG(aligned16(d_a) && aligned16(d_b) && aligned16(idx) && aligned16(dx),
+               w + ": pointers must be 16-byte aligned");
+  const int64_t ib = g.in_vecs * 16, ob = g.out_vecs * 16, xb = g.out_vecs * 8;
+  GS_CHECK_ARG(!overlap(dx, ib, d_a, ob) && !overlap(dx, ib, d_b, ob) && !overlap(dx, ib, idx, xb),
+               w + ": dx overlaps an input");
+  const dim3 grid(static_cast<unsigned>((g.out_vecs + kBlock - 1) / kBlock)), block(kBlock);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint16_t* ap = static_cast<const uint16_t*>(d_a);
+  const uint16_t* bp = static_cast<const uint16_t*>(d_b);
+  const uint8_t* ip = static_cast<const uint8_t*>(idx);
+  uint16_t* op = static_cast<uint16_t*>(dx);
+  if (bp)
+    hipLaunchKernelGGL((maxpool_bwd_kernel<true>), grid, block, 0, s, ap, bp, ip, op, g.out_vecs, H, W, g.OH, g.OW,
+                       C / 8);
+  else
+    hipLaunchKernelGGL((maxpool_bwd_kernel<false>), grid, block, 0, s, ap, bp, ip, op, g.out_vecs, H, W, g.OH, g.OW,
+                       C / 8);
   HIP_RET(hipGetLastError());
   return GS_OK;
 }

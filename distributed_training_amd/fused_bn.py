@@ -17,6 +17,16 @@ masked gradient once: it is the identity branch's gradient and the dx pass's
 input.  Saved for backward are x, y, weight, mean and invstd — what the stock
 path keeps alive too.  Deterministic, no host synchronisation, capturable.
 
+``fork=True`` returns the output as two tensors over one storage, for an output
+with two consumers (a residual block's: the next block's first convolution and
+its identity branch).  Autograd then hands ``backward`` the two gradients
+unsummed and ``gs_bn_bwd_reduce_fork`` adds them (bf16 round-to-nearest, ATen's
+``add``) in the pass that reads them anyway.  ``bn_relu_pool(bn, x, pool)`` is
+the stem: the BatchNorm forward, then ``gs_relu_maxpool_fwd`` pools over relu(.)
+and keeps a byte per output (no in-place ReLU pass, no int64 indices); backward,
+``gs_maxpool_bwd`` writes the BatchNorm's dy once from those bytes and the one
+or two pooled gradients (no zero fill, no atomics, no add).
+
 The fused path engages only for: CUDA, training mode, 4-D channels_last bf16
 input, fp32 affine weights, C % 8 == 0, no forward hooks on the module, the
 library loaded, and ``GSYNC_FUSED_BN`` not ``0``.  Everything else (CPU, fp32,
@@ -66,7 +76,7 @@ def _eligible(bn, x, relu, residual) -> bool:
 
 class _BnAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, bn, momentum, relu):
+    def forward(ctx, x, weight, bias, residual, bn, momentum, relu, fork=False):
         y, mean, invstd, _, _ = torch._batch_norm_impl_index(
             x, weight, bias, bn.running_mean, bn.running_var, True, momentum, bn.eps, torch.backends.cudnn.enabled)
         if not y.is_contiguous(memory_format=_CL):
@@ -79,14 +89,24 @@ class _BnAct(torch.autograd.Function):
         ctx.relu = relu
         ctx.has_residual = residual is not None
         ctx.save_for_backward(x, weight, mean, invstd, y if relu else None)
+        if fork:
+            # two tensors over one storage: autograd hands backward their gradients unsummed
+            ctx.set_materialize_grads(False)
+            return y, y.view_as(y)
         return y
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, dy):
+    def backward(ctx, dy, dy_b=None):
         x, weight, mean, invstd, y = ctx.saved_tensors
+        if dy is None:
+            dy, dy_b = dy_b, None
+        if dy is None:  # neither half of a fork was used
+            return None, None, None, None, None, None, None, None
         if not dy.is_contiguous(memory_format=_CL):
             dy = dy.contiguous(memory_format=_CL)
+        if dy_b is not None and not dy_b.is_contiguous(memory_format=_CL):
+            dy_b = dy_b.contiguous(memory_format=_CL)
         C = x.shape[1]
         R = x.numel() // C
         ws = torch.empty(_n_partials(R, C) * C * 2, dtype=torch.float32, device=x.device)
@@ -96,7 +116,14 @@ class _BnAct(torch.autograd.Function):
         lib, stream = L.lib(), L.stream_ptr(x.device)
         yp = y.data_ptr() if ctx.relu else None
         g = None
-        if ctx.has_residual:
+        if dy_b is not None:
+            # the fork's sum, the mask and the sums in one pass; g is what ATen's add + threshold_backward left
+            g = torch.empty_like(x)
+            L.check(lib.gs_bn_bwd_reduce_fork(x.data_ptr(), dy.data_ptr(), dy_b.data_ptr(), yp, g.data_ptr(),
+                                              mean.data_ptr(), ws.data_ptr(), ws.numel(), R, C, stream),
+                    "gs_bn_bwd_reduce_fork")
+            dy, yp = g, None
+        elif ctx.has_residual:
             g = torch.empty_like(x)
             L.check(lib.gs_bn_bwd_reduce(x.data_ptr(), dy.data_ptr(), yp, g.data_ptr(), mean.data_ptr(),
                                          ws.data_ptr(), ws.numel(), R, C, stream), "gs_bn_bwd_reduce")
@@ -107,23 +134,112 @@ class _BnAct(torch.autograd.Function):
         L.check(lib.gs_bn_bwd_dx(x.data_ptr(), dy.data_ptr(), yp, mean.data_ptr(), invstd.data_ptr(),
                                  weight.data_ptr(), ws.data_ptr(), ws.numel(), dx.data_ptr(), gw.data_ptr(),
                                  gb.data_ptr(), R, C, stream), "gs_bn_bwd_dx")
-        return dx, gw, gb, g, None, None, None
+        return dx, gw, gb, g if ctx.has_residual else None, None, None, None, None
 
 
-def bn_act(bn, x, relu: bool = True, residual=None):
-    """``relu(bn(x) + residual)``; ``relu=False`` / ``residual=None`` drop that part."""
+class _BnReluPool(torch.autograd.Function):
+    """MaxPool2d(3, 2, 1)(relu(bn(x))): the ReLU is taken while pooling, the BatchNorm output stays
+    un-ReLU'd (its sign is the ReLU mask), the pool keeps one byte per output instead of int64 indices."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, momentum, fork):
+        y, mean, invstd, _, _ = torch._batch_norm_impl_index(
+            x, weight, bias, bn.running_mean, bn.running_var, True, momentum, bn.eps, torch.backends.cudnn.enabled)
+        if not y.is_contiguous(memory_format=_CL):
+            raise RuntimeError("fused_bn: batch_norm returned a layout other than its channels_last input's")
+        N, C, H, W = y.shape
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        out = torch.empty((N, C, OH, OW), dtype=y.dtype, device=y.device, memory_format=_CL)
+        idx = torch.empty((N, OH, OW, C), dtype=torch.uint8, device=y.device)
+        L.check(L.lib().gs_relu_maxpool_fwd(y.data_ptr(), out.data_ptr(), idx.data_ptr(), N, H, W, C,
+                                            L.stream_ptr(y.device)), "gs_relu_maxpool_fwd")
+        ctx.save_for_backward(x, weight, mean, invstd, y, idx)
+        if fork:
+            ctx.set_materialize_grads(False)
+            return out, out.view_as(out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_a, d_b=None):
+        x, weight, mean, invstd, y, idx = ctx.saved_tensors
+        if d_a is None:
+            d_a, d_b = d_b, None
+        if d_a is None:
+            return None, None, None, None, None, None
+        if not d_a.is_contiguous(memory_format=_CL):
+            d_a = d_a.contiguous(memory_format=_CL)
+        if d_b is not None and not d_b.is_contiguous(memory_format=_CL):
+            d_b = d_b.contiguous(memory_format=_CL)
+        N, C, H, W = x.shape
+        R = N * H * W
+        lib, stream = L.lib(), L.stream_ptr(x.device)
+        dy = torch.empty_like(x)
+        L.check(lib.gs_maxpool_bwd(d_a.data_ptr(), None if d_b is None else d_b.data_ptr(), idx.data_ptr(),
+                                   dy.data_ptr(), N, H, W, C, stream), "gs_maxpool_bwd")
+        ws = torch.empty(_n_partials(R, C) * C * 2, dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        gw = torch.empty_like(weight)
+        gb = torch.empty_like(weight)
+        L.check(lib.gs_bn_bwd_reduce(x.data_ptr(), dy.data_ptr(), y.data_ptr(), None, mean.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), R, C, stream), "gs_bn_bwd_reduce")
+        L.check(lib.gs_bn_bwd_dx(x.data_ptr(), dy.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                 weight.data_ptr(), ws.data_ptr(), ws.numel(), dx.data_ptr(), gw.data_ptr(),
+                                 gb.data_ptr(), R, C, stream), "gs_bn_bwd_dx")
+        return dx, gw, gb, None, None, None
+
+
+def _bookkeeping(bn) -> float:
+    """nn.BatchNorm2d.forward's bookkeeping (T:nn/modules/batchnorm.py, _BatchNorm.forward) -> momentum"""
+    momentum = 0.0 if bn.momentum is None else bn.momentum
+    if bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+        if bn.momentum is None:
+            momentum = 1.0 / float(bn.num_batches_tracked)
+    return momentum
+
+
+def _pool_eligible(pool) -> bool:
+    def is_(v, k):
+        return v == k or v == (k, k) or v == [k, k]
+
+    return (type(pool) is torch.nn.MaxPool2d and is_(pool.kernel_size, 3) and is_(pool.stride, 2)
+            and is_(pool.padding, 1) and is_(pool.dilation, 1) and not pool.ceil_mode and not pool.return_indices
+            and not (pool._forward_pre_hooks or pool._forward_hooks))
+
+
+def bn_relu_pool(bn, x, pool, fork: bool = True):
+    """``pool(relu(bn(x)))`` for the stem; ``fork`` as in ``bn_act``.
+
+    Fused (under ``bn_act``'s conditions, for a hook-free ``MaxPool2d(3, 2, 1)``): the BatchNorm forward,
+    then one launch that pools over relu(.) and keeps the winner's window position in a byte; backward,
+    one launch from those bytes and the one or two pooled gradients to the BatchNorm backward's dy.
+    Anything else is the stock ``pool(bn_act(bn, x))``."""
+    global last_path
+    if _pool_eligible(pool) and _eligible(bn, x, True, None):
+        momentum = _bookkeeping(bn)
+        last_path = "fused"
+        return _BnReluPool.apply(x, bn.weight, bn.bias, bn, momentum, fork)
+    out = pool(bn_act(bn, x))
+    return (out, out) if fork else out
+
+
+def bn_act(bn, x, relu: bool = True, residual=None, fork: bool = False):
+    """``relu(bn(x) + residual)``; ``relu=False`` / ``residual=None`` drop that part.
+
+    ``fork=True`` returns the result twice, for a caller that feeds it to two consumers (a block's
+    output: the next block's first convolution and its identity branch).  On the fused path the two
+    tensors alias one storage and their gradients are summed inside the BatchNorm backward's first
+    pass; on the stock path it is the same tensor twice and autograd sums as ever."""
     global last_path
     if _eligible(bn, x, relu, residual):
-        # nn.BatchNorm2d.forward's bookkeeping (T:nn/modules/batchnorm.py, _BatchNorm.forward)
-        momentum = 0.0 if bn.momentum is None else bn.momentum
-        if bn.track_running_stats and bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-            if bn.momentum is None:
-                momentum = 1.0 / float(bn.num_batches_tracked)
+        momentum = _bookkeeping(bn)
         last_path = "fused"
-        return _BnAct.apply(x, bn.weight, bn.bias, residual, bn, momentum, relu)
+        return _BnAct.apply(x, bn.weight, bn.bias, residual, bn, momentum, relu, fork)
     last_path = "stock"
     out = bn(x)
     if residual is not None:
         out += residual
-    return F.relu(out, inplace=True) if relu else out
+    if relu:
+        out = F.relu(out, inplace=True)
+    return (out, out) if fork else out

@@ -14,13 +14,20 @@ Every BatchNorm runs through ``fused_bn.bn_act`` together with the ReLU and the
 residual add that follow it: on an MI355X training step (bf16, channels_last)
 that takes libgsync's fused backward kernels; everywhere else it is the stock
 ``relu(bn(x) + identity)``.
+
+A block's output has two consumers, the next block's first convolution and its
+identity (or downsample) branch.  ``ResNet.forward`` therefore drives the blocks
+of ``layer1..4`` through ``forward_pair``: every block but the last returns its
+output as the pair ``bn_act(..., fork=True)`` gives, whose two gradients the
+fused BatchNorm backward sums in its first pass (no separate add).  Called with
+one tensor, a block or a layer is what it always was.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from .fused_bn import bn_act
+from .fused_bn import bn_act, bn_relu_pool
 
 
 def conv3x3(in_planes, out_planes, stride=1):
@@ -49,12 +56,16 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
         self.stride = stride
 
-    def forward(self, x):
-        identity = x
+    def forward_pair(self, pair, fork_out):
+        """pair: the input twice (main path, identity path); fork_out: return the output as a pair too"""
+        x, identity = pair
         if self.downsample is not None:
-            identity = _downsample(self.downsample, x)
+            identity = _downsample(self.downsample, identity)
         out = bn_act(self.bn1, self.conv1(x))
-        return bn_act(self.bn2, self.conv2(out), residual=identity)
+        return bn_act(self.bn2, self.conv2(out), residual=identity, fork=fork_out)
+
+    def forward(self, x):
+        return self.forward_pair((x, x), False)
 
 
 class Bottleneck(nn.Module):
@@ -72,13 +83,17 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
         self.stride = stride
 
-    def forward(self, x):
-        identity = x
+    def forward_pair(self, pair, fork_out):
+        """pair: the input twice (main path, identity path); fork_out: return the output as a pair too"""
+        x, identity = pair
         if self.downsample is not None:
-            identity = _downsample(self.downsample, x)
+            identity = _downsample(self.downsample, identity)
         out = bn_act(self.bn1, self.conv1(x))
         out = bn_act(self.bn2, self.conv2(out))
-        return bn_act(self.bn3, self.conv3(out), residual=identity)
+        return bn_act(self.bn3, self.conv3(out), residual=identity, fork=fork_out)
+
+    def forward(self, x):
+        return self.forward_pair((x, x), False)
 
 
 class ResNet(nn.Module):
@@ -115,9 +130,22 @@ class ResNet(nn.Module):
             layers.append(block(self.inplanes, planes))
         return nn.Sequential(*layers)
 
+    def _hooked(self):
+        """a forward hook on a layer or a block: only their own calls run it"""
+        return any(m._forward_hooks or m._forward_pre_hooks
+                   for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for m in (layer, *layer))
+
     def forward(self, x):
-        x = self.maxpool(bn_act(self.bn1, self.conv1(x)))
-        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        x = self.conv1(x)
+        if self._hooked():
+            x = bn_relu_pool(self.bn1, x, self.maxpool, fork=False)
+            x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        else:
+            blocks = [b for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer]
+            pair = bn_relu_pool(self.bn1, x, self.maxpool, fork=True)
+            for b in blocks[:-1]:
+                pair = b.forward_pair(pair, True)
+            x = blocks[-1].forward_pair(pair, False)
         x = torch.flatten(self.avgpool(x), 1)
         return self.fc(x)
 

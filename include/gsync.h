@@ -727,6 +727,13 @@ int gs_bn_bwd_partials(int64_t R, int C);
  * threshold_backward(dy, y, 0)), the gradient of a residual branch. */
 int gs_bn_bwd_reduce(const void* x, const void* dy, const void* y, void* g_out, const float* mean, float* ws,
                      int64_t ws_floats, int64_t R, int C, void* stream);
+/* the same for an activation whose gradient arrives as the two halves of a fork:
+ * dy = bf16(float(dy_a) + float(dy_b)), rounded to nearest even (bit-identical to
+ * ATen's bf16 add), then the mask (y != NULL), g_out and the sums as above.
+ * g_out is required (with or without y) and overlaps no input: it is the
+ * gradient the dx pass reads, with y = NULL.  dy_b = NULL: gs_bn_bwd_reduce. */
+int gs_bn_bwd_reduce_fork(const void* x, const void* dy_a, const void* dy_b, const void* y, void* g_out,
+                          const float* mean, float* ws, int64_t ws_floats, int64_t R, int C, void* stream);
 /* folds the partials in index order and writes
  * dx = weight * invstd * (g - sum(g)/R - xhat * sum(g*xhat)/R) as bf16
  * (truncated, as the MIOpen kernels it replaces convert it),
@@ -738,6 +745,19 @@ int gs_bn_bwd_dx(const void* x, const void* dy, const void* y, const float* mean
  * formed in fp32 and rounded once to bf16, then max with 0; bit-identical to
  * ATen's add_ followed by relu_ */
 int gs_add_relu_fwd(void* t, const void* identity, int64_t n, void* stream);
+/* the stem's tail: pooled = MaxPool2d(3, stride 2, padding 1)(relu(y)) over an NHWC bf16 activation
+ * [N, H, W, C] -> [N, OH, OW, C], OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, and idx [N, OH, OW, C]
+ * uint8: the winner's position 3 * kh + kw (0..8) in its unclipped 3 x 3 window.  y is left as it is.
+ * The winner is chosen as ATen's relu_ + max_pool2d choose it (rows outer, columns inner, a later
+ * value wins only if it is greater or NaN), so pooled is bit-identical to theirs. */
+int gs_relu_maxpool_fwd(const void* y, void* pooled, void* idx, int64_t N, int H, int W, int C, void* stream);
+/* the pool's backward from idx: dx [N, H, W, C] bf16, every element written (no zero fill, no
+ * atomics): the sum of the gradients of the windows that name the element, windows in ascending
+ * (oh, ow) order, added in fp32 and rounded once to bf16; bit-identical to ATen's
+ * max_pool2d_with_indices_backward.  d_b != NULL: a window's gradient is bf16(d_a + d_b), the two
+ * halves of a fork of the pooled output (ATen's bf16 add). */
+int gs_maxpool_bwd(const void* d_a, const void* d_b, const void* idx, void* dx, int64_t N, int H, int W, int C,
+                   void* stream);
 
 #ifdef __cplusplus
 }
