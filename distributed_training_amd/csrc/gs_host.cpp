@@ -415,30 +415,41 @@ int host_ema(gs_plan* p, int sdt, int ldt, float w, int copy) {
 }
 
 // LARS on the host (include/gsync.h, gs_lars_step): the same contract as the device
-// kernels — fp32, every multiply and add rounded once, no fma.  The per-tensor sums
-// run in element order, 1 Ki-element blocks folded front to back: a fixed order
-// (serial, so the thread count does not enter), not the device's.
-int host_lars_norms(gs_plan* p, int gdt, float* norms) {
+// kernels — fp32, every multiply and add rounded once, no fma.  The per-tensor sums of
+// LARS and LAMB are one loop: element order, 1 Ki-element blocks folded front to back — a
+// fixed order (serial, so the thread count does not enter), not the device's.
+// tensor(t) returns the element function of tensor t: (i, a, b) -> the operands of the
+// two squares of element i.
+template <class Tensor>
+static void blockwise_sq_sums(const gs_plan* p, float* norms, Tensor&& tensor) {
   constexpr int64_t kBlk = 1024;
+  for (int t = 0; t < p->n; ++t) {
+    auto elem = tensor(t);
+    float sa = 0.f, sb = 0.f;
+    for (int64_t i0 = 0; i0 < p->numel[t]; i0 += kBlk) {
+      const int64_t i1 = std::min(p->numel[t], i0 + kBlk);
+      float ba = 0.f, bb = 0.f;
+      for (int64_t i = i0; i < i1; ++i) {
+        float a, b;
+        elem(i, a, b);
+        ba = ba + a * a;
+        bb = bb + b * b;
+      }
+      sa = sa + ba;
+      sb = sb + bb;
+    }
+    norms[2 * t] = sa;
+    norms[2 * t + 1] = sb;
+  }
+}
+
+int host_lars_norms(gs_plan* p, int gdt, float* norms) {
   GS_HOST_FLOAT(gdt, GD, {
-    for (int t = 0; t < p->n; ++t) {
+    blockwise_sq_sums(p, norms, [&](int t) {
       const float* pp = static_cast<const float*>(slot(p, 0, t));
       const void* gp = slot(p, 1, t);
-      float sp = 0.f, sg = 0.f;
-      for (int64_t i0 = 0; i0 < p->numel[t]; i0 += kBlk) {
-        const int64_t i1 = std::min(p->numel[t], i0 + kBlk);
-        float bp = 0.f, bg = 0.f;
-        for (int64_t i = i0; i < i1; ++i) {
-          const float x = pp[i], g = ldT<GD>(gp, i);
-          bp = bp + x * x;
-          bg = bg + g * g;
-        }
-        sp = sp + bp;
-        sg = sg + bg;
-      }
-      norms[2 * t] = sp;
-      norms[2 * t + 1] = sg;
-    }
+      return [=](int64_t i, float& x, float& g) { x = pp[i]; g = ldT<GD>(gp, i); };
+    });
   });
   return GS_OK;
 }
@@ -479,43 +490,28 @@ int host_lars(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* nor
 
 // LAMB on the host (include/gsync.h, gs_lamb_moments / gs_lamb_step): the device kernels'
 // contract and the same text of the update (lamb_moments / lamb_update / lamb_coef,
-// gs_common.h).  Sums in element order, 1 Ki-element blocks folded front to back, as
-// host_lars_norms.
+// gs_common.h).  The sums are host_lars_norms' loop, with u in place of g; the element
+// function also writes m', v'.
 int host_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, const float* gsc, const float* fi) {
-  constexpr int64_t kBlk = 1024;
   GS_TRY_RET(check_float(gdt));
   if (fi && fi[0] != 0.f) return GS_OK;
   const bool has_m = gsc != nullptr;
   const float mul = gsc ? gsc[0] : 1.f;
   GS_HOST_FLOAT(gdt, GD, {
-    for (int t = 0; t < p->n; ++t) {
+    blockwise_sq_sums(p, norms, [&](int t) {
       const float* pp = static_cast<const float*>(slot(p, 0, t));
       const void* gp = slot(p, 1, t);
       float* mp = static_cast<float*>(slot(p, 2, t));
       float* vp = static_cast<float*>(slot(p, 3, t));
       const float wd_t = (p->adapt.empty() || p->adapt[t] != 0) ? h.wd : 0.f;
-      float sp = 0.f, su = 0.f;
-      for (int64_t i0 = 0; i0 < p->numel[t]; i0 += kBlk) {
-        const int64_t i1 = std::min(p->numel[t], i0 + kBlk);
-        float bp = 0.f, bu = 0.f;
-        for (int64_t i = i0; i < i1; ++i) {
-          float g = ldT<GD>(gp, i);
-          if (has_m) g = g * mul;
-          float m = mp[i], v = vp[i];
-          lamb_moments(h, g, &m, &v);
-          const float x = pp[i];
-          const float u = lamb_update(h, x, m, v, wd_t);
-          mp[i] = m;
-          vp[i] = v;
-          bp = bp + x * x;
-          bu = bu + u * u;
-        }
-        sp = sp + bp;
-        su = su + bu;
-      }
-      norms[2 * t] = sp;
-      norms[2 * t + 1] = su;
-    }
+      return [=](int64_t i, float& x, float& u) {
+        float g = ldT<GD>(gp, i);
+        if (has_m) g = g * mul;
+        lamb_moments(h, g, &mp[i], &vp[i]);
+        x = pp[i];
+        u = lamb_update(h, x, mp[i], vp[i], wd_t);
+      };
+    });
   });
   return GS_OK;
 }

@@ -1,9 +1,10 @@
 // gfx950 (CDNA4) fused SGD / Adam(W) / LARS updates of libgsync (gs_sgd_step / gs_adam_step /
 // gs_lars_step[_lowp]): the chunk-map engine of gs_engine.h with SgdOp / AdamOp / LarsOp, the
-// grad-load policy per launch; LARS's per-tensor Σp², Σg² (gs_lars_norms), a segmented
-// reduction over the same chunk map; and LAMB (gs_lamb_moments / gs_lamb_step): that
-// reduction fused with the moments' read-modify-write, then LambOp on the engine; and the
-// EMA / SWA weight average (gs_ema_step / gs_ema_hyper): EmaOp on the engine.
+// grad-load policy per launch; the segmented per-tensor-sum pass over the same chunk map
+// (seg_sum_kernel), one skeleton with two lane policies: LarsLanes, LARS's Σp², Σg²
+// (gs_lars_norms), and LambLanes, LAMB's Σp², Σu² fused with the moments' read-modify-write
+// (gs_lamb_moments); LambOp on the engine (gs_lamb_step); and the EMA / SWA weight average
+// (gs_ema_step / gs_ema_hyper): EmaOp on the engine.
 
 #include "gs_engine.h"
 
@@ -87,13 +88,13 @@ int hip_ema_hyper(int64_t* n_averaged, int mode, double decay, float* hyper, voi
   return GS_OK;
 }
 
-// ------------------------------------------------------------------- LARS
-// Per-tensor Σp², Σg² (gs_lars_norms): a segmented reduction on the chunk map.  The
-// host numbers one partial slot per (chunk, tensor intersecting it) pair, in chunk
-// order then tensor order — a full chunk has one, a mixed chunk of span k has k —
+// ------------------------------------------------- segmented per-tensor sums
+// Two sums per tensor (LARS: Σp², Σg²; LAMB: Σp², Σu²): a segmented reduction on the chunk
+// map.  The host numbers one partial slot per (chunk, tensor intersecting it) pair, in
+// chunk order then tensor order — a full chunk has one, a mixed chunk of span k has k —
 // so a tensor's slots are the contiguous range [first, first + count).  Every slot
 // is written by exactly one workgroup, with a sum whose order the chunk alone fixes:
-//   full chunk   each lane squares its 4 + 4 elements in element order, then the
+//   full chunk   each lane squares its 4 + 4 values in element order, then the
 //                fixed DPP tree per wave and the 4 wave sums in wave order;
 //   mixed chunk  each lane leaves its two sums in LDS; lanes of one tensor are
 //                contiguous, and thread i adds up tensor t0 + i's lane range in
@@ -102,13 +103,23 @@ int hip_ema_hyper(int64_t* n_averaged, int mode, double decay, float* hyper, voi
 // lars_norm_finish then folds each tensor's slots with one workgroup: thread j adds slots
 // j, j + 256, ... in order, then the same fixed tree.  Nothing depends on the grid or on
 // arrival order and there are no floating-point atomics: replicas holding the same
-// p and g publish the same bits.
-// Both streams take plain cached loads: the update re-reads the same bytes right
-// behind, and a ResNet-50's p + g (204 MB) fit the Infinity Cache.
+// inputs publish the same bits.
+// The walk, the order and the slot writes are seg_sum_kernel's, written once.  A lane
+// policy L says what a lane does with its 4 elements:
+//   S, GD, NTG, NTS  its streams: the plan's slots 0..S-1, fp32 but for the grads (slot 1,
+//                    dtype GD); non-temporal loads of the grads / of the others.  A chunk
+//                    takes the 16-B accesses when the align bits of all S streams are set
+//   W                streams W..S-1 are stored back (non-temporal, as every store of the engine)
+//   G                chunks per workgroup iteration (sizes s_red)
+//   begin()          at kernel entry, uniform over the grid: false = nothing to do
+//   lane<U>(t, valid, r, a, b)  the lane's two sums from its registers r[S][4], of which
+//                    `valid` elements are the tensor's (the rest were loaded as zeros); may
+//                    rewrite r.  U: t is wave-uniform (a full chunk), per-tensor values are
+//                    then scalar loads (cload)
 struct LarsMap {
   const int32_t* cb;  // [n_chunks]: first partial slot of each chunk
   const int32_t* tb;  // [2n]: first slot, slot count of each tensor
-  float* part;        // [2 * slots]: Σp², Σg² per slot
+  float* part;        // [2 * slots]: the two sums per slot
 };
 
 template <int K>
@@ -142,27 +153,87 @@ __device__ __forceinline__ float lars_sq4(const float (&x)[4]) {
   return s;
 }
 
-// the lane's 4 + 4 elements of full chunk c of tensor t (uniform descriptor loads)
-template <int GD>
-__device__ __forceinline__ void lars_full_load(const PlanArgs& P, int t, int64_t c, float (&x)[4], float (&g)[4]) {
-  const void* pp = cload(P.ptrs, t);
-  const void* gp = cload(P.ptrs, static_cast<int64_t>(P.n) + t);
-  const uint32_t a = cload(P.align, t);
-  const int64_t e0 = c * kChunkElems - cload(P.voff, t);
-  const uint32_t lo = threadIdx.x * kUnit;
-  if ((a & 3u) == 3u) {
-    load4F<GS_F32>(elem_at<GS_F32>(pp, e0), lo, x);
-    load4F<GD>(elem_at<GD>(gp, e0), lo, g);
-  } else {
-    const int64_t n = cload(P.numel, t);
-    loadN<GS_F32, 4>(pp, e0 + lo, n, false, x);
-    loadN<GD, 4>(gp, e0 + lo, n, false, g);
+// The lane's 4 elements of streams K..S-1 of policy L (loads) or W..S-1 (stores): F = the
+// full chunk's 16-B accesses at e0 + lo, else loadN / storeN with bit k of `vec` = stream
+// k's base is 16-B aligned.  K is a template index: non-temporal is a property of the load
+// instruction, and two arms under a run-time k are merged into one cached load.
+template <class L, bool F, int K = 0>
+__device__ __forceinline__ void seg_load(void* const (&ptr)[L::S], int64_t e0, uint32_t lo, int64_t n, uint32_t vec,
+                                         float (&r)[L::S][4]) {
+  if constexpr (K < L::S) {
+    ld<K == 1 ? L::GD : GS_F32, 4, F, K == 1 ? L::NTG : L::NTS>(ptr[K], e0, lo, n, ((vec >> K) & 1u) != 0, r[K]);
+    seg_load<L, F, K + 1>(ptr, e0, lo, n, vec, r);
+  }
+}
+template <class L, bool F, int K = L::W>
+__device__ __forceinline__ void seg_store(void* const (&ptr)[L::S], int64_t e0, uint32_t lo, int64_t n, uint32_t vec,
+                                          const float (&r)[L::S][4]) {
+  if constexpr (K < L::S) {
+    st<GS_F32, 4, F>(ptr[K], e0, lo, n, ((vec >> K) & 1u) != 0, r[K]);
+    seg_store<L, F, K + 1>(ptr, e0, lo, n, vec, r);
   }
 }
 
-template <int GD>
-__device__ __forceinline__ void lars_mixed(const PlanArgs& P, const LarsMap& M, int t0, int span, int64_t c,
-                                           float* s_p, float* s_g) {
+template <int S>
+struct SegChunk {  // full chunk c of tensor t, S streams (uniform descriptor loads: SGPRs)
+  void* ptr[S];
+  int64_t e0, n;  // the chunk's first element inside the tensor; numel (read only when !vec)
+  bool vec;       // the align bits of all S streams are set
+};
+template <int S>
+__device__ __forceinline__ SegChunk<S> seg_chunk(const PlanArgs& P, int t, int64_t c) {
+  constexpr uint32_t kAll = (1u << S) - 1;
+  SegChunk<S> d;
+#pragma unroll
+  for (int k = 0; k < S; ++k) d.ptr[k] = cload(P.ptrs, k * static_cast<int64_t>(P.n) + t);
+  d.e0 = c * kChunkElems - cload(P.voff, t);
+  d.vec = (cload(P.align, t) & kAll) == kAll;
+  d.n = d.vec ? 0 : cload(P.numel, t);
+  return d;
+}
+
+// K full chunks c0, c0 + 1, ... of tensors t[0..K): all S * K loads of a lane in flight,
+// then per chunk the lane's work and stores, then one barrier pair for the 2 * K sums and
+// the K slot writes
+template <class L, int K>
+__device__ __forceinline__ void seg_full(const PlanArgs& P, const LarsMap& M, const L& lanes, const int* t,
+                                         int64_t c0, float* s_red) {
+  constexpr int S = L::S;
+  const uint32_t lo = threadIdx.x * kUnit;
+  float r[K][S][4], v[2 * K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const SegChunk<S> d = seg_chunk<S>(P, t[j], c0 + j);
+    if (d.vec) seg_load<L, true>(d.ptr, d.e0, lo, 0, 0, r[j]);
+    else seg_load<L, false>(d.ptr, d.e0, lo, d.n, 0, r[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    lanes.template lane<true>(t[j], 4, r[j], v[2 * j], v[2 * j + 1]);
+    if constexpr (L::W < S) {
+      const SegChunk<S> d = seg_chunk<S>(P, t[j], c0 + j);
+      if (d.vec) seg_store<L, true>(d.ptr, d.e0, lo, 0, 0, r[j]);
+      else seg_store<L, false>(d.ptr, d.e0, lo, d.n, 0, r[j]);
+    }
+  }
+  lars_block_sum<2 * K>(v, s_red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int64_t s = cload(M.cb, c0 + j);
+      M.part[2 * s] = v[2 * j];
+      M.part[2 * s + 1] = v[2 * j + 1];
+    }
+  }
+}
+
+// a mixed chunk (tensor tails, runs of small tensors, any span): per-lane descriptor
+// loads; loadN / storeN mask the tensor's tail and take the scalar path on an unaligned
+// stream
+template <class L>
+__device__ __forceinline__ void seg_mixed(const PlanArgs& P, const LarsMap& M, const L& lanes, int t0, int span,
+                                          int64_t c, float* s_a, float* s_b) {
+  constexpr int S = L::S;
   const int64_t cs = c * kChunkElems;
   const int64_t e = cs + static_cast<int>(threadIdx.x) * kUnit;
   int lo = t0, hi = t0 + span - 1;
@@ -170,20 +241,22 @@ __device__ __forceinline__ void lars_mixed(const PlanArgs& P, const LarsMap& M, 
     const int mid = (lo + hi + 1) >> 1;
     if (P.voff[mid] <= e) lo = mid; else hi = mid - 1;
   }
-  float sp = 0.f, sg = 0.f;
+  float sa = 0.f, sb = 0.f;
   const int64_t local = e - P.voff[lo];
   const int64_t n = P.numel[lo];
   if (local >= 0 && local < n) {  // else: an alignment gap between tensors
     const uint32_t a = P.align[lo];
-    float x[4], g[4];
-    loadN<GS_F32, 4>(P.ptrs[lo], local, n, (a & 1u) != 0, x);
-    loadN<GD, 4>(P.ptrs[static_cast<int64_t>(P.n) + lo], local, n, (a & 2u) != 0, g);
-    sp = lars_sq4(x);
-    sg = lars_sq4(g);
+    void* ptr[S];  // all pointers first: a pointer load between two data loads would wait for the first
+#pragma unroll
+    for (int k = 0; k < S; ++k) ptr[k] = P.ptrs[k * static_cast<int64_t>(P.n) + lo];
+    float r[S][4];
+    seg_load<L, false>(ptr, local, 0, n, a, r);
+    lanes.template lane<false>(lo, static_cast<int>(std::min<int64_t>(4, n - local)), r, sa, sb);
+    seg_store<L, false>(ptr, local, 0, n, a, r);
   }
   __syncthreads();  // the previous mixed chunk's readers are done with the stage
-  s_p[threadIdx.x] = sp;
-  s_g[threadIdx.x] = sg;
+  s_a[threadIdx.x] = sa;
+  s_b[threadIdx.x] = sb;
   __syncthreads();
   const int slot0 = M.cb[c];
   for (int i = static_cast<int>(threadIdx.x); i < span; i += kBlock) {
@@ -191,28 +264,24 @@ __device__ __forceinline__ void lars_mixed(const PlanArgs& P, const LarsMap& M, 
     const int64_t b = P.voff[t] - cs, end = b + P.numel[t];  // the tensor's range, relative to the chunk
     const int l0 = b <= 0 ? 0 : static_cast<int>(std::min<int64_t>(kBlock, b / kUnit));
     const int l1 = end <= 0 ? 0 : static_cast<int>(std::min<int64_t>(kBlock, (end + kUnit - 1) / kUnit));
-    float ap = 0.f, ag = 0.f;
+    float ta = 0.f, tb = 0.f;
     for (int l = l0; l < l1; ++l) {
-      ap = ap + s_p[l];
-      ag = ag + s_g[l];
+      ta = ta + s_a[l];
+      tb = tb + s_b[l];
     }
-    M.part[2 * static_cast<int64_t>(slot0 + i)] = ap;
-    M.part[2 * static_cast<int64_t>(slot0 + i) + 1] = ag;
+    M.part[2 * static_cast<int64_t>(slot0 + i)] = ta;
+    M.part[2 * static_cast<int64_t>(slot0 + i) + 1] = tb;
   }
 }
 
-// chunks per workgroup iteration: a group of kLarsG full chunks (of one tensor or
-// several: every chunk has its own slot) has all 2 * kLarsG accesses of a lane in
-// flight before one barrier pair
-#ifndef GS_G_LARS_NORM
-#define GS_G_LARS_NORM 4
-#endif
-constexpr int kLarsG = GS_G_LARS_NORM;
-
-template <int GD>
-__global__ void __launch_bounds__(kBlock) GS_SGPR_ATTR lars_norm_kernel(PlanArgs P, LarsMap M) {
-  constexpr int G = kLarsG;
-  __shared__ float s_p[kBlock], s_g[kBlock], s_red[2 * G * (kBlock / 64)];
+// a workgroup iteration takes a group of G chunks: G full chunks (of one tensor or
+// several: every chunk has its own slot) go through seg_full at once; otherwise chunk by
+// chunk, skipping the empty ones (code < 0: inside the plan, or past its end)
+template <class L>
+__global__ void __launch_bounds__(kBlock) GS_SGPR_ATTR seg_sum_kernel(PlanArgs P, LarsMap M, L lanes) {
+  constexpr int G = L::G;
+  __shared__ float s_a[kBlock], s_b[kBlock], s_red[2 * G * (kBlock / 64)];
+  if (!lanes.begin()) return;  // ahead of every barrier: nothing is written
   const int* cw = &P.chunks[0].t0;  // [t0, code] pairs
   const int64_t n_groups = (static_cast<int64_t>(P.n_chunks) + G - 1) / G;
   for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
@@ -227,41 +296,13 @@ __global__ void __launch_bounds__(kBlock) GS_SGPR_ATTR lars_norm_kernel(PlanArgs
       all_full = all_full && code[j] == 0;
     }
     if (all_full) {
-      float x[G][4], y[G][4], v[2 * G];
-#pragma unroll
-      for (int j = 0; j < G; ++j) lars_full_load<GD>(P, t[j], c0 + j, x[j], y[j]);
-#pragma unroll
-      for (int j = 0; j < G; ++j) {
-        v[2 * j] = lars_sq4(x[j]);
-        v[2 * j + 1] = lars_sq4(y[j]);
-      }
-      lars_block_sum<2 * G>(v, s_red);
-      if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-          const int64_t s = cload(M.cb, c0 + j);
-          M.part[2 * s] = v[2 * j];
-          M.part[2 * s + 1] = v[2 * j + 1];
-        }
-      }
+      seg_full<L, G>(P, M, lanes, t, c0, s_red);
       continue;
     }
 #pragma unroll
     for (int j = 0; j < G; ++j) {
-      const int64_t c = c0 + j;
-      if (code[j] == 0) {
-        float x[4], y[4];
-        lars_full_load<GD>(P, t[j], c, x, y);
-        float v[2] = {lars_sq4(x), lars_sq4(y)};
-        lars_block_sum<2>(v, s_red);
-        if (threadIdx.x == 0) {
-          const int64_t s = cload(M.cb, c);
-          M.part[2 * s] = v[0];
-          M.part[2 * s + 1] = v[1];
-        }
-      } else if (code[j] > 0) {
-        lars_mixed<GD>(P, M, t[j], code[j], c, s_p, s_g);
-      }
+      if (code[j] == 0) seg_full<L, 1>(P, M, lanes, &t[j], c0 + j, s_red);
+      else if (code[j] > 0) seg_mixed(P, M, lanes, t[j], code[j], c0 + j, s_a, s_b);
     }
   }
 }
@@ -353,12 +394,10 @@ int hip_lars_set_adapt(gs_plan* p) {
   return GS_OK;
 }
 
-// A chunk pass that writes the plan's partial slots (G chunks per workgroup iteration),
-// then lars_norm_finish: the launch timer takes the pair as one record of `kind`, the
-// chunk pass's start and the fold's stop.  pass(grid, s, ev0, a, m) launches the chunk
-// pass (ev0 != NULL: with that start event).
-template <class Pass>
-static int lars_segmented(gs_plan* p, float* norms, void* stream, int kind, int G, Pass&& pass) {
+// seg_sum_kernel<L> over the plan's chunks, then lars_norm_finish: the launch timer takes
+// the pair as one record of `kind`, the chunk pass's start and the fold's stop.
+template <class L>
+static int lars_segmented(gs_plan* p, float* norms, void* stream, int kind, const L& lanes) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   GS_TRY_RET(lars_prepare(p, stream));
   GS_TRY_RET(hip_plan_flush(p, stream));
@@ -369,11 +408,14 @@ static int lars_segmented(gs_plan* p, float* norms, void* stream, int kind, int 
   hipEvent_t ev1 = nslots ? static_cast<hipEvent_t>(p->timer_ev[2 * tk + 1]) : nullptr;
   const LarsMap m{reinterpret_cast<const int32_t*>(p->d_lars), reinterpret_cast<const int32_t*>(lars_tb_ptr(p)),
                   reinterpret_cast<float*>(lars_part_ptr(p))};
-  const int64_t groups = (static_cast<int64_t>(p->chunks.size()) + G - 1) / G;
+  const int64_t groups = (static_cast<int64_t>(p->chunks.size()) + L::G - 1) / L::G;
   if (groups > 0) {
     const int grid = static_cast<int>(std::min<int64_t>(groups, p->grid_cap));
     const PlanArgs a = p->args();
-    GS_TRY_RET(pass(grid, s, ev0, a, m));
+    if (ev0)
+      hipExtLaunchKernelGGL((seg_sum_kernel<L>), dim3(grid), dim3(kBlock), 0, s, ev0, nullptr, 0, a, m, lanes);
+    else
+      hipLaunchKernelGGL((seg_sum_kernel<L>), dim3(grid), dim3(kBlock), 0, s, a, m, lanes);
     HIP_RET(hipGetLastError());
     ev0 = nullptr;
   }
@@ -394,19 +436,33 @@ static int lars_segmented(gs_plan* p, float* norms, void* stream, int kind, int 
   return GS_OK;
 }
 
+// ------------------------------------------------------------------- LARS
+// gs_lars_norms: Σp², Σg², two streams and no stores.  Both take plain cached loads: the
+// update re-reads the same bytes right behind, and a ResNet-50's p + g (204 MB) fit the
+// Infinity Cache.  A group of kLarsG full chunks has all 2 * kLarsG accesses of a lane in
+// flight before one barrier pair.
+#ifndef GS_G_LARS_NORM
+#define GS_G_LARS_NORM 4
+#endif
+constexpr int kLarsG = GS_G_LARS_NORM;
+
+template <int GD_>
+struct LarsLanes {
+  static constexpr int G = kLarsG, S = 2, W = 2, GD = GD_;
+  static constexpr bool NTG = false, NTS = false;
+  __device__ __forceinline__ bool begin() { return true; }
+  template <bool U>
+  __device__ __forceinline__ void lane(int, int, float (&r)[S][4], float& sp, float& sg) const {
+    sp = lars_sq4(r[0]);
+    sg = lars_sq4(r[1]);
+  }
+};
+
 int hip_lars_norms(gs_plan* p, int gdt, float* norms, void* stream) {
   DeviceGuard g(p->device);
   if (p->n == 0) return GS_OK;
-  return lars_segmented(p, norms, stream, GS_OP_LARS_NORM, kLarsG,
-                        [&](int grid, hipStream_t s, hipEvent_t ev0, const PlanArgs& a, const LarsMap& m) -> int {
-    GS_DISPATCH_FLOAT(gdt, GD, {
-      if (ev0)
-        hipExtLaunchKernelGGL((lars_norm_kernel<GD>), dim3(grid), dim3(kBlock), 0, s, ev0, nullptr, 0, a, m);
-      else
-        hipLaunchKernelGGL((lars_norm_kernel<GD>), dim3(grid), dim3(kBlock), 0, s, a, m);
-    });
-    return GS_OK;
-  });
+  GS_DISPATCH_FLOAT(gdt, GD, return lars_segmented(p, norms, stream, GS_OP_LARS_NORM, LarsLanes<GD>{}));
+  return GS_OK;
 }
 
 // ldt = -1: LarsOp<.., -1, ..>, the op without a copy stream (gs_lars_step)
@@ -433,230 +489,67 @@ int hip_lars(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* norm
 
 // ------------------------------------------------------------------- LAMB
 // gs_lamb_moments: LAMB's trust ratio needs the norm of the Adam update u, so the norm
-// pass is also the moments pass — an element-wise read-modify-write of (m, v) and the
-// segmented reduction of gs_lars_norms in one kernel.  The slot map, the order inside a
-// chunk and the fold (lars_norm_finish) are LARS's, with u² in place of g²: per full
-// chunk each lane squares its 4 + 4 values in element order, then the DPP tree and the
-// 4 wave sums in wave order; per mixed chunk thread i adds up tensor t0 + i's lanes in
-// lane order.  m', v' are stored (non-temporal, as every store of the engine); u is not:
-// LambOp recomputes it from (p, m', v') by the same text (lamb_update).
+// pass is also the moments pass — the segmented pass over four streams (p, g, m, v) with
+// an element-wise read-modify-write of (m, v), and u² in place of LARS's g².  m', v' are
+// stored; u is not: LambOp recomputes it from (p, m', v') by the same text (lamb_update).
 // Load policy (measured: profiles/lamb/): non-temporal loads of g (dead
 // after this pass), cached loads of p, m, v (re-read by the update).  GS_LAMB_NT is the
 // compile-time switch of the A/B library variants: bit 0 = g, bit 1 = p, m, v.
 #ifndef GS_LAMB_NT
 #define GS_LAMB_NT 1
 #endif
-constexpr bool kLambNTG = (GS_LAMB_NT & 1) != 0, kLambNTS = (GS_LAMB_NT & 2) != 0;
-struct LambMomArgs {
-  LambHyper h;
-  const int32_t* adapt;  // [n]
-  const float* gscale;
-  const float* found_inf;
-  const float* hyper;  // [lr, bc1, bc2s] in device memory (gs_plan_set_hyper_source) or NULL
-};
-
 #ifndef GS_G_LAMB_MOMENTS
 #define GS_G_LAMB_MOMENTS 4
 #endif
 constexpr int kLambG = GS_G_LAMB_MOMENTS;
 
-// the lane's 4 elements: the new moments in place and the lane's Σp², Σu² (`valid`
-// elements are the tensor's; the rest were loaded as zeros and add nothing: with eps = 0
-// their u would be 0/0)
-__device__ __forceinline__ void lamb_lane(const LambHyper& h, bool has_m, float mul, float wd_t, int valid,
-                                          const float (&x)[4], const float (&g)[4], float (&m)[4], float (&v)[4],
-                                          float& sp, float& su) {
-  float u[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float gi = g[i];
-    if (has_m) gi = gi * mul;
-    lamb_moments(h, gi, &m[i], &v[i]);
-    const float ui = lamb_update(h, x[i], m[i], v[i], wd_t);
-    u[i] = i < valid ? ui : 0.f;
-  }
-  sp = lars_sq4(x);
-  su = lars_sq4(u);
-}
-
-// the lane's 4 + 4 + 4 + 4 elements of full chunk c of tensor t (uniform descriptor loads)
-template <int GD, bool NTG, bool NTS>
-__device__ __forceinline__ void lamb_full_load(const PlanArgs& P, int t, int64_t c, float (&x)[4], float (&g)[4],
-                                               float (&m)[4], float (&v)[4]) {
-  const int64_t n1 = P.n;
-  const void* pp = cload(P.ptrs, t);
-  const void* gp = cload(P.ptrs, n1 + t);
-  const void* mp = cload(P.ptrs, 2 * n1 + t);
-  const void* vp = cload(P.ptrs, 3 * n1 + t);
-  const int64_t e0 = c * kChunkElems - cload(P.voff, t);
-  const uint32_t lo = threadIdx.x * kUnit;
-  if ((cload(P.align, t) & 15u) == 15u) {
-    load4F<GS_F32, NTS>(elem_at<GS_F32>(pp, e0), lo, x);
-    load4F<GD, NTG>(elem_at<GD>(gp, e0), lo, g);
-    load4F<GS_F32, NTS>(elem_at<GS_F32>(mp, e0), lo, m);
-    load4F<GS_F32, NTS>(elem_at<GS_F32>(vp, e0), lo, v);
-  } else {
-    const int64_t n = cload(P.numel, t);
-    loadN<GS_F32, 4, NTS>(pp, e0 + lo, n, false, x);
-    loadN<GD, 4, NTG>(gp, e0 + lo, n, false, g);
-    loadN<GS_F32, 4, NTS>(mp, e0 + lo, n, false, m);
-    loadN<GS_F32, 4, NTS>(vp, e0 + lo, n, false, v);
-  }
-}
-__device__ __forceinline__ void lamb_full_store(const PlanArgs& P, int t, int64_t c, const float (&m)[4],
-                                                const float (&v)[4]) {
-  const int64_t n1 = P.n;
-  void* mp = cload(P.ptrs, 2 * n1 + t);
-  void* vp = cload(P.ptrs, 3 * n1 + t);
-  const int64_t e0 = c * kChunkElems - cload(P.voff, t);
-  const uint32_t lo = threadIdx.x * kUnit;
-  if ((cload(P.align, t) & 15u) == 15u) {
-    store4F<GS_F32>(const_cast<void*>(elem_at<GS_F32>(mp, e0)), lo, m);
-    store4F<GS_F32>(const_cast<void*>(elem_at<GS_F32>(vp, e0)), lo, v);
-  } else {
-    const int64_t n = cload(P.numel, t);
-    storeN<GS_F32, 4>(mp, e0 + lo, n, false, m);
-    storeN<GS_F32, 4>(vp, e0 + lo, n, false, v);
-  }
-}
-
-// a mixed chunk (tensor tails, runs of small tensors, any span): lars_mixed with the
-// moments' read-modify-write; loadN / storeN mask the tensor's tail and take the scalar
-// path on an unaligned stream
-template <int GD, bool NTG, bool NTS>
-__device__ __forceinline__ void lamb_mixed(const PlanArgs& P, const LarsMap& M, const LambMomArgs& A,
-                                           const LambHyper& h, bool has_m, float mul, int t0, int span, int64_t c,
-                                           float* s_p, float* s_u) {
-  const int64_t cs = c * kChunkElems;
-  const int64_t e = cs + static_cast<int>(threadIdx.x) * kUnit;
-  int lo = t0, hi = t0 + span - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (P.voff[mid] <= e) lo = mid; else hi = mid - 1;
-  }
-  float sp = 0.f, su = 0.f;
-  const int64_t local = e - P.voff[lo];
-  const int64_t n = P.numel[lo];
-  if (local >= 0 && local < n) {  // else: an alignment gap between tensors
-    const uint32_t a = P.align[lo];
-    const int64_t n1 = P.n;
-    void* mp = P.ptrs[2 * n1 + lo];
-    void* vp = P.ptrs[3 * n1 + lo];
-    float x[4], g[4], m[4], v[4];
-    loadN<GS_F32, 4, NTS>(P.ptrs[lo], local, n, (a & 1u) != 0, x);
-    loadN<GD, 4, NTG>(P.ptrs[n1 + lo], local, n, (a & 2u) != 0, g);
-    loadN<GS_F32, 4, NTS>(mp, local, n, (a & 4u) != 0, m);
-    loadN<GS_F32, 4, NTS>(vp, local, n, (a & 8u) != 0, v);
-    const int valid = static_cast<int>(std::min<int64_t>(4, n - local));
-    lamb_lane(h, has_m, mul, A.adapt[lo] != 0 ? h.wd : 0.f, valid, x, g, m, v, sp, su);
-    storeN<GS_F32, 4>(mp, local, n, (a & 4u) != 0, m);
-    storeN<GS_F32, 4>(vp, local, n, (a & 8u) != 0, v);
-  }
-  __syncthreads();  // the previous mixed chunk's readers are done with the stage
-  s_p[threadIdx.x] = sp;
-  s_u[threadIdx.x] = su;
-  __syncthreads();
-  const int slot0 = M.cb[c];
-  for (int i = static_cast<int>(threadIdx.x); i < span; i += kBlock) {
-    const int t = t0 + i;
-    const int64_t b = P.voff[t] - cs, end = b + P.numel[t];  // the tensor's range, relative to the chunk
-    const int l0 = b <= 0 ? 0 : static_cast<int>(std::min<int64_t>(kBlock, b / kUnit));
-    const int l1 = end <= 0 ? 0 : static_cast<int>(std::min<int64_t>(kBlock, (end + kUnit - 1) / kUnit));
-    float ap = 0.f, au = 0.f;
-    for (int l = l0; l < l1; ++l) {
-      ap = ap + s_p[l];
-      au = au + s_u[l];
+template <int GD_>
+struct LambLanes {
+  static constexpr int G = kLambG, S = 4, W = 2, GD = GD_;
+  static constexpr bool NTG = (GS_LAMB_NT & 1) != 0, NTS = (GS_LAMB_NT & 2) != 0;
+  LambHyper h;
+  const int32_t* adapt;  // [n]
+  const float* gscale;
+  const float* found_inf;
+  const float* hyper;  // [lr, bc1, bc2s] in device memory (gs_plan_set_hyper_source) or NULL
+  float mul;           // *gscale, read by begin()
+  __device__ __forceinline__ bool begin() {
+    if (found_inf != nullptr && *found_inf != 0.f) return false;
+    if (hyper) {
+      h.bc1 = hyper[1];
+      h.bc2s = hyper[2];
     }
-    M.part[2 * static_cast<int64_t>(slot0 + i)] = ap;
-    M.part[2 * static_cast<int64_t>(slot0 + i) + 1] = au;
+    mul = gscale != nullptr ? *gscale : 1.f;
+    return true;
   }
-}
-
-template <int GD, bool NTG, bool NTS>
-__global__ void __launch_bounds__(kBlock) GS_SGPR_ATTR lamb_moments_kernel(PlanArgs P, LarsMap M, LambMomArgs A) {
-  constexpr int G = kLambG;
-  __shared__ float s_p[kBlock], s_u[kBlock], s_red[2 * G * (kBlock / 64)];
-  if (A.found_inf != nullptr && *A.found_inf != 0.f) return;  // uniform across the grid: nothing is written
-  LambHyper h = A.h;
-  if (A.hyper) {
-    h.bc1 = A.hyper[1];
-    h.bc2s = A.hyper[2];
+  // the new moments in place and the lane's Σp², Σu² (the elements past `valid` add
+  // nothing: with eps = 0 their u would be 0/0)
+  template <bool U>
+  __device__ __forceinline__ void lane(int t, int valid, float (&r)[S][4], float& sp, float& su) const {
+    const float wd_t = (U ? cload(adapt, t) : adapt[t]) != 0 ? h.wd : 0.f;
+    float u[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float gi = r[1][i];
+      if (gscale != nullptr) gi = gi * mul;
+      lamb_moments(h, gi, &r[2][i], &r[3][i]);
+      const float ui = lamb_update(h, r[0][i], r[2][i], r[3][i], wd_t);
+      u[i] = i < valid ? ui : 0.f;
+    }
+    sp = lars_sq4(r[0]);
+    su = lars_sq4(u);
   }
-  const bool has_m = A.gscale != nullptr;
-  const float mul = has_m ? *A.gscale : 1.f;
-  const int* cw = &P.chunks[0].t0;  // [t0, code] pairs
-  const int64_t n_groups = (static_cast<int64_t>(P.n_chunks) + G - 1) / G;
-  for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
-    const int64_t c0 = G * g;
-    int t[G], code[G];
-    bool all_full = true;
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      const bool in = c0 + j < P.n_chunks;
-      t[j] = in ? cload(cw, 2 * (c0 + j)) : -1;
-      code[j] = in ? cload(cw, 2 * (c0 + j) + 1) : -1;
-      all_full = all_full && code[j] == 0;
-    }
-    if (all_full) {
-      // all 4 * G loads of a lane in flight, then per chunk: moments, stores, the two sums
-      float x[G][4], y[G][4], m[G][4], v[G][4], r[2 * G];
-#pragma unroll
-      for (int j = 0; j < G; ++j) lamb_full_load<GD, NTG, NTS>(P, t[j], c0 + j, x[j], y[j], m[j], v[j]);
-#pragma unroll
-      for (int j = 0; j < G; ++j) {
-        const float wd_t = cload(A.adapt, t[j]) != 0 ? h.wd : 0.f;
-        lamb_lane(h, has_m, mul, wd_t, 4, x[j], y[j], m[j], v[j], r[2 * j], r[2 * j + 1]);
-        lamb_full_store(P, t[j], c0 + j, m[j], v[j]);
-      }
-      lars_block_sum<2 * G>(r, s_red);
-      if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-          const int64_t s = cload(M.cb, c0 + j);
-          M.part[2 * s] = r[2 * j];
-          M.part[2 * s + 1] = r[2 * j + 1];
-        }
-      }
-      continue;
-    }
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      const int64_t c = c0 + j;
-      if (code[j] == 0) {
-        float x[4], y[4], m[4], v[4], r[2];
-        lamb_full_load<GD, NTG, NTS>(P, t[j], c, x, y, m, v);
-        lamb_lane(h, has_m, mul, cload(A.adapt, t[j]) != 0 ? h.wd : 0.f, 4, x, y, m, v, r[0], r[1]);
-        lamb_full_store(P, t[j], c, m, v);
-        lars_block_sum<2>(r, s_red);
-        if (threadIdx.x == 0) {
-          const int64_t s = cload(M.cb, c);
-          M.part[2 * s] = r[0];
-          M.part[2 * s + 1] = r[1];
-        }
-      } else if (code[j] > 0) {
-        lamb_mixed<GD, NTG, NTS>(P, M, A, h, has_m, mul, t[j], code[j], c, s_p, s_u);
-      }
-    }
-  }
-}
+};
 
 int hip_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, const float* gsc, const float* fi,
                      void* stream) {
   DeviceGuard g(p->device);
   if (p->n == 0) return GS_OK;
-  GS_TRY_RET(lars_prepare(p, stream));  // A.adapt below points into the scratch
-  const LambMomArgs A{h, reinterpret_cast<const int32_t*>(lars_adapt_ptr(p)), gsc, fi, p->hyper};
-  return lars_segmented(p, norms, stream, GS_OP_LAMB_MOMENTS, kLambG,
-                        [&](int grid, hipStream_t s, hipEvent_t ev0, const PlanArgs& a, const LarsMap& m) -> int {
-    GS_DISPATCH_FLOAT(gdt, GD, {
-      if (ev0)
-        hipExtLaunchKernelGGL((lamb_moments_kernel<GD, kLambNTG, kLambNTS>), dim3(grid), dim3(kBlock), 0, s, ev0,
-                              nullptr, 0, a, m, A);
-      else
-        hipLaunchKernelGGL((lamb_moments_kernel<GD, kLambNTG, kLambNTS>), dim3(grid), dim3(kBlock), 0, s, a, m, A);
-    });
-    return GS_OK;
-  });
+  GS_TRY_RET(lars_prepare(p, stream));  // adapt below points into the scratch
+  const int32_t* adapt = reinterpret_cast<const int32_t*>(lars_adapt_ptr(p));
+  GS_DISPATCH_FLOAT(gdt, GD, return lars_segmented(p, norms, stream, GS_OP_LAMB_MOMENTS,
+                                                   LambLanes<GD>{h, adapt, gsc, fi, p->hyper, 1.f}));
+  return GS_OK;
 }
 
 int hip_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const float* fi, void* stream) {

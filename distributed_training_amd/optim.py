@@ -99,7 +99,31 @@ def _check_dense(p: torch.Tensor, g: torch.Tensor, what: str, seen: dict | None 
         seen[id(p)] = ps
 
 
+def _sq_norms(self) -> list:
+    """[(params, norms)] per plan of the last step (FusedLARS, FusedLAMB): ``norms`` is
+    the fp32[2n] tensor the step published, [2t] = Σp², [2t+1] = Σg² (LARS) or Σu² (LAMB)
+    of ``params[t]`` (of the values before the update; overwritten by the next step)."""
+    return list(self._last_norms)
+
+
+def _bind_adapt(self, plan, group, ps):
+    """The plan's per-tensor adaptation flags from ``group["adapt"]`` and its 2n norm
+    scratch ``plan._norms`` (FusedLARS, FusedLAMB), set when the flags change."""
+    adapt = group.get("adapt")
+    flags = tuple((p.ndim > 1) if adapt is None else bool(adapt) for p in ps)
+    if getattr(plan, "_adapt", None) != flags:
+        if _capturing():
+            raise RuntimeError(f"{self._name}: take one eager step before capturing "
+                               "(the plan's adaptation flags and scratch are set there)")
+        plan.set_adapt(flags)
+        plan._adapt = flags
+        plan._norms = torch.zeros(2 * len(ps), dtype=torch.float32, device=ps[0].device)
+
+
 class _FusedBase(torch.optim.Optimizer):
+    _name: str  # the class in error messages (a subclass under another name keeps its parent's)
+    _timer_kinds: tuple  # GS_OP_* of the launches kernel_ms() reports
+
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._plans = _PlanCache()
@@ -153,11 +177,52 @@ class _FusedBase(torch.optim.Optimizer):
                 plan.timer_enable(n_slots)
 
     def kernel_ms(self) -> list:
-        """Update-kernel durations (ms) since the last call, all plans (the
-        Σg² launches of max_grad_norm are left out)."""
-        kind = L.GS_OP_ADAM if isinstance(self, FusedAdam) else L.GS_OP_SGD
+        """Durations (ms) of the class's kernels (the updates; LARS / LAMB: the norm /
+        moments passes, then the updates) since the last call, all plans (the Σg²
+        launches of max_grad_norm are left out)."""
         return [ms for plan in self._plans.plans() if plan.kind == L.GS_DEV_HIP
-                for ms in plan.timer_read(kind=kind)]
+                for k, v in plan.timer_read_by_kind().items() if k in self._timer_kinds for ms in v]
+
+    def _check_param(self, p):
+        """A parameter with a grad: dense grad in the parameter's layout, fp32 parameter."""
+        if p.grad.is_sparse:
+            raise RuntimeError(f"{self._name} does not support sparse gradients")
+        _check_dense(p, p.grad, self._name, self._dense_seen)
+        if p.dtype != torch.float32:
+            raise RuntimeError(f"{self._name} expects fp32 parameters (keep a fp32 master copy)")
+
+    def _clip_buffer(self, device):
+        """[published Σg², coef, norm | accumulated raw Σg² (several plans)] of `device`"""
+        buf = self._clip_buf.get(device)
+        if buf is None:
+            buf = self._clip_buf[device] = torch.zeros(4, dtype=torch.float32, device=device)
+        return buf
+
+    def _collect(self, group, by_first=False):
+        """{key: (params, grads, momentum buffers)} of the group's parameters with a grad
+        (FusedSGD, FusedLARS); a missing buffer is created as zeros.  key = the grad dtype;
+        by_first (FusedSGD): (grad dtype, this step created the buffer) — its kernel has a
+        first-step form — and every parameter gets its (maybe empty) state entry."""
+        out = {}
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            self._check_param(p)
+            buf, first = None, False
+            st = self.state[p] if group["momentum"] != 0 or by_first else None
+            if group["momentum"] != 0:
+                buf = st.get("momentum_buffer")
+                first = buf is None
+                if first:
+                    if _capturing():
+                        raise RuntimeError(f"{self._name}: momentum buffers must exist before capture "
+                                           "(take an eager step first)")
+                    buf = st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            ps, gs, bs = out.setdefault((p.grad.dtype, first) if by_first else p.grad.dtype, ([], [], []))
+            ps.append(p)
+            gs.append(p.grad)
+            bs.append(buf)
+        return out
 
     def _device_state(self) -> bool:
         """Step-varying state on the device: capturable mode, the AMP path
@@ -180,11 +245,7 @@ class _FusedBase(torch.optim.Optimizer):
         the unfused path."""
         if not self.defaults.get("max_grad_norm"):
             raise ValueError("fuse_grad_norm_into: the optimizer has no max_grad_norm")
-        dev = ddp.device
-        buf = self._clip_buf.get(dev)
-        if buf is None:
-            buf = self._clip_buf[dev] = torch.zeros(4, dtype=torch.float32, device=dev)
-        ddp.set_grad_sqnorm_target(buf[3:4])
+        ddp.set_grad_sqnorm_target(self._clip_buffer(ddp.device)[3:4])
         self._norm_ddp = (ddp, frozenset(id(p) for p in ddp._params))
 
     def _ddp_sqnorm(self, device):
@@ -230,13 +291,8 @@ class _FusedBase(torch.optim.Optimizer):
                     plan.set_clip(None)
                     plan._clip_on = False
             return self.grad_scale
-        buf = self._clip_buf.get(device)
-        if buf is None:
-            # [published Σg², coef, norm | accumulated raw Σg² (several plans)]
-            buf = torch.zeros(4, dtype=torch.float32, device=device)
-            self._clip_buf[device] = buf
-        sq, coef, norm = buf[0:1], buf[1:2], buf[2:3]
-        self.last_grad_norm = norm
+        buf = self._clip_buffer(device)
+        self.last_grad_norm = buf[2:3]
         if CLIP_FUSED:
             fused = self._ddp_sqnorm(device)
             if fused is not None:
@@ -269,10 +325,7 @@ class _FusedBase(torch.optim.Optimizer):
         coefficient min(1, max_norm/(‖g‖+1e-6)) (times grad_scale) by gs_clip_coef
         into the clip buffer [Σg², coef, norm, -], returned as the grad multiplier."""
         max_norm = self.defaults.get("max_grad_norm")
-        buf = self._clip_buf.get(device)
-        if buf is None:
-            buf = torch.zeros(4, dtype=torch.float32, device=device)
-            self._clip_buf[device] = buf
+        buf = self._clip_buffer(device)
         sq, coef, norm = buf[0:1], buf[1:2], buf[2:3]
         self.last_grad_norm = norm
         for plan, _ in all_plans:
@@ -309,29 +362,8 @@ class FusedSGD(_FusedBase):
                         fused=fused, max_grad_norm=max_grad_norm, capturable=bool(capturable))
         super().__init__(params, defaults)
 
-    def _collect(self, group):
-        out = {}  # (grad dtype, has_buf) -> lists
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            if p.grad.is_sparse:
-                raise RuntimeError("FusedSGD does not support sparse gradients")
-            _check_dense(p, p.grad, "FusedSGD", self._dense_seen)
-            if p.dtype != torch.float32:
-                raise RuntimeError("FusedSGD expects fp32 parameters (keep a fp32 master copy)")
-            st = self.state[p]
-            buf = st.get("momentum_buffer")
-            first = group["momentum"] != 0 and buf is None
-            if group["momentum"] != 0 and buf is None:
-                buf = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["momentum_buffer"] = buf
-            key = (p.grad.dtype, first)
-            out.setdefault(key, ([], [], []))
-            ps, gs, bs = out[key]
-            ps.append(p)
-            gs.append(p.grad)
-            bs.append(buf)
-        return out
+    _name = "FusedSGD"
+    _timer_kinds = (L.GS_OP_SGD,)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -339,14 +371,10 @@ class FusedSGD(_FusedBase):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        new_bufs = any(group["momentum"] != 0 and p.grad is not None and "momentum_buffer" not in self.state[p]
-                       for group in self.param_groups for p in group["params"])
-        if new_bufs and _capturing():
-            raise RuntimeError("FusedSGD: momentum buffers must exist before capture (take an eager step first)")
         dev_state = self._device_state()
         work = []
         for gi, group in enumerate(self.param_groups):
-            for (gdt, first), (ps, gs, bs) in self._collect(group).items():
+            for (gdt, first), (ps, gs, bs) in self._collect(group, by_first=True).items():
                 plan = self._plans.get(ps)
                 plan.set_ptrs(0, ps)
                 plan.set_ptrs(1, gs)
@@ -434,42 +462,10 @@ class FusedLARS(_FusedBase):
         super().__init__(params, defaults)
         self._last_norms: list = []
 
-    def kernel_ms(self) -> list:
-        """Durations (ms) of the norm passes and the updates since the last call, all plans."""
-        kinds = (L.GS_OP_LARS_NORM, L.GS_OP_LARS)
-        return [ms for plan in self._plans.plans() if plan.kind == L.GS_DEV_HIP
-                for k, v in plan.timer_read_by_kind().items() if k in kinds for ms in v]
-
-    def sq_norms(self) -> list:
-        """[(params, norms)] per plan of the last step: ``norms`` is the fp32[2n]
-        tensor the step published, [2t] = Σp², [2t+1] = Σg² of ``params[t]``
-        (of the values before the update; overwritten by the next step)."""
-        return list(self._last_norms)
-
-    def _collect(self, group):
-        out = {}  # grad dtype -> lists
-        for p in group["params"]:
-            if p.grad is None:
-                continue
-            if p.grad.is_sparse:
-                raise RuntimeError("FusedLARS does not support sparse gradients")
-            _check_dense(p, p.grad, "FusedLARS", self._dense_seen)
-            if p.dtype != torch.float32:
-                raise RuntimeError("FusedLARS expects fp32 parameters (keep a fp32 master copy)")
-            buf = None
-            if group["momentum"] != 0:
-                st = self.state[p]
-                buf = st.get("momentum_buffer")
-                if buf is None:
-                    if _capturing():
-                        raise RuntimeError("FusedLARS: momentum buffers must exist before capture "
-                                           "(take an eager step first)")
-                    buf = st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            ps, gs, bs = out.setdefault(p.grad.dtype, ([], [], []))
-            ps.append(p)
-            gs.append(p.grad)
-            bs.append(buf)
-        return out
+    _name = "FusedLARS"
+    _timer_kinds = (L.GS_OP_LARS_NORM, L.GS_OP_LARS)
+    sq_norms = _sq_norms
+    _bind_adapt = _bind_adapt
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -486,15 +482,7 @@ class FusedLARS(_FusedBase):
                 plan.set_ptrs(1, gs)
                 if group["momentum"] != 0:
                     plan.set_ptrs(2, bs)
-                adapt = group.get("adapt")
-                flags = tuple((p.ndim > 1) if adapt is None else bool(adapt) for p in ps)
-                if getattr(plan, "_adapt", None) != flags:
-                    if _capturing():
-                        raise RuntimeError("FusedLARS: take one eager step before capturing "
-                                           "(the plan's adaptation flags and scratch are set there)")
-                    plan.set_adapt(flags)
-                    plan._adapt = flags
-                    plan._lars_norms = torch.zeros(2 * len(ps), dtype=torch.float32, device=ps[0].device)
+                self._bind_adapt(plan, group, ps)
                 if dev_state:
                     h = self._group_hyper(gi, group, ps[0].device)
                     if getattr(plan, "_hyper", None) is not h["hyper"]:
@@ -502,18 +490,82 @@ class FusedLARS(_FusedBase):
                 work.append((group, plan, gdt, ps))
         if dev_state:
             self.refresh_hyper()
-        self._last_norms = [(ps, plan._lars_norms) for _, plan, _, ps in work]
+        self._last_norms = [(ps, plan._norms) for _, plan, _, ps in work]
         for group, plan, gdt, ps in work:
-            plan.lars_norms(gdt, plan._lars_norms)
+            plan.lars_norms(gdt, plan._norms)
             plan.lars(gdt, group["lr"], group["momentum"], group["weight_decay"], group["trust_coefficient"],
-                      group["eps"], plan._lars_norms, grad_scale=self.grad_scale, found_inf=self.found_inf)
+                      group["eps"], plan._norms, grad_scale=self.grad_scale, found_inf=self.found_inf)
         return loss
 
 
 class _DeviceSteps:
-    """The Adam-family step counters (FusedAdam, FusedLAMB)."""
+    """The Adam-family state and step counters (FusedAdam, FusedLAMB)."""
 
-    _name = "FusedAdam"
+    def _gather(self, cap):
+        """Create missing state, advance the host steps (not `cap`) or adopt / split the
+        device-counter cohorts (`cap`), and bind one plan per (group, grad dtype, step |
+        cohort): slots 0..3 = p, g, exp_avg, exp_avg_sq, and under `cap` the cohort's hyper
+        source.  Returns the work list in launch order, entries (group, plan, gdt, step,
+        params): plan None = advance the counter of cohort c and form its hyper source
+        (step = (h, c)); else step = the host step value, None under `cap` (the kernels
+        read the hyper source)."""
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            buckets: dict = {}
+            by_cohort: dict = {}
+            h = None
+            live = []
+
+            def add(key, p):
+                st = self.state[p]
+                for lst, x in zip(buckets.setdefault(key, ([], [], [], [])),
+                                  (p, p.grad, st["exp_avg"], st["exp_avg_sq"])):
+                    lst.append(x)
+
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                self._check_param(p)
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    if _capturing():
+                        raise RuntimeError(f"{self._name}: state must exist before capture (take an eager step first)")
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                live.append(p)
+            # every state of this step exists before cohorts are formed: parameters
+            # whose state starts together share one cohort (one counter, one plan)
+            for p in live:
+                st = self.state[p]
+                if cap:
+                    if h is None:
+                        h = self._group_hyper(gi, group, p.device)
+                    if id(st["step"]) not in h.get("cohorts", {}):
+                        self._adopt_cohorts(h, group)
+                    by_cohort.setdefault(id(st["step"]), []).append(p)
+                else:
+                    st["step"] += 1
+                    add((p.grad.dtype, float(st["step"].item())), p)
+            for cid, ps in by_cohort.items():
+                c = h["cohorts"][cid]
+                if len(ps) < len(c["members"]):
+                    c = self._split_cohort(h, c, ps)
+                work.append((group, None, None, (h, c), None))
+                for p in ps:
+                    add((p.grad.dtype, id(c["step"])), p)
+            cohort_hyper = {id(c["step"]): c["hyper"] for c in h["cohorts"].values()} if h is not None else {}
+            for (gdt, step), lists in buckets.items():
+                plan = self._plans.get(lists[0])
+                for slot, lst in enumerate(lists):
+                    plan.set_ptrs(slot, lst)
+                if cap:
+                    hyper = cohort_hyper[step]
+                    if getattr(plan, "_hyper", None) is not hyper:
+                        plan.set_hyper_source(hyper)
+                    step = None
+                work.append((group, plan, gdt, step, lists[0]))
+        return work
 
     # ---- device step counters (capturable / AMP): one fp64 counter per cohort of
     # parameters that have advanced together so far.  torch keeps one step per
@@ -577,6 +629,9 @@ class _DeviceSteps:
 class FusedAdam(_DeviceSteps, _FusedBase):
     """Adam (``adamw=False``) or AdamW (``adamw=True`` / ``decoupled_weight_decay=True``)."""
 
+    _name = "FusedAdam"
+    _timer_kinds = (L.GS_OP_ADAM,)
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
                  *, foreach=None, maximize=False, capturable=False, differentiable=False, fused=None,
                  decoupled_weight_decay=False, adamw=None, max_grad_norm=None):
@@ -603,80 +658,14 @@ class FusedAdam(_DeviceSteps, _FusedBase):
             with torch.enable_grad():
                 loss = closure()
         cap = self._device_state()  # device step counters: capturable or AMP (no host read of found_inf)
-        work = []
-        for gi, group in enumerate(self.param_groups):
-            buckets = {}
-            by_cohort: dict = {}
-            h = None
-            live = []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.grad.is_sparse:
-                    raise RuntimeError("FusedAdam does not support sparse gradients")
-                _check_dense(p, p.grad, "FusedAdam", self._dense_seen)
-                if p.dtype != torch.float32:
-                    raise RuntimeError("FusedAdam expects fp32 parameters (keep a fp32 master copy)")
-                st = self.state[p]
-                if len(st) == 0 or "exp_avg" not in st:
-                    if _capturing():
-                        raise RuntimeError("FusedAdam: state must exist before capture (take an eager step first)")
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                live.append(p)
-            # every state of this step exists before cohorts are formed: parameters
-            # whose state starts together share one cohort (one counter, one plan)
-            for p in live:
-                st = self.state[p]
-                if cap:
-                    if h is None:
-                        h = self._group_hyper(gi, group, p.device)
-                    if id(st["step"]) not in h.get("cohorts", {}):
-                        self._adopt_cohorts(h, group)
-                    by_cohort.setdefault(id(st["step"]), []).append(p)
-                else:
-                    st["step"] += 1
-                    lists = buckets.setdefault((p.grad.dtype, float(st["step"].item())), ([], [], [], []))
-                    lists[0].append(p)
-                    lists[1].append(p.grad)
-                    lists[2].append(st["exp_avg"])
-                    lists[3].append(st["exp_avg_sq"])
-            for cid, ps in by_cohort.items():
-                c = h["cohorts"][cid]
-                if len(ps) < len(c["members"]):
-                    c = self._split_cohort(h, c, ps)
-                work.append((group, None, gi, (h, c)))  # advance the cohort's counter, form its hyper source
-                for p in ps:
-                    st = self.state[p]
-                    lists = buckets.setdefault((p.grad.dtype, id(c["step"])), ([], [], [], []))
-                    lists[0].append(p)
-                    lists[1].append(p.grad)
-                    lists[2].append(st["exp_avg"])
-                    lists[3].append(st["exp_avg_sq"])
-            cohort_hyper = {id(c["step"]): c["hyper"] for c in h["cohorts"].values()} if h is not None else {}
-            for (gdt, step), (ps, gs, ms, vs) in buckets.items():
-                plan = self._plans.get(ps)
-                plan.set_ptrs(0, ps)
-                plan.set_ptrs(1, gs)
-                plan.set_ptrs(2, ms)
-                plan.set_ptrs(3, vs)
-                if cap:
-                    hyper = cohort_hyper[step]
-                    if getattr(plan, "_hyper", None) is not hyper:
-                        plan.set_hyper_source(hyper)
-                    work.append((group, plan, gdt, None))
-                else:
-                    work.append((group, plan, gdt, step))
-        if not work:
-            return loss
-        if cap:
-            self.refresh_hyper()
+        work = self._gather(cap)
         plans = [(w[1], w[2]) for w in work if w[1] is not None]
         if not plans:
             return loss
+        if cap:
+            self.refresh_hyper()
         scale = self._clip_scale(plans[0][0].device, plans)
-        for group, plan, gdt, step in work:
+        for group, plan, gdt, step, _ in work:
             beta1, beta2 = group["betas"]
             if plan is None:  # device counters: advance the cohort's step, form its hyper source
                 h, c = step
@@ -746,6 +735,9 @@ class FusedLAMB(_DeviceSteps, _FusedBase):
     """
 
     _name = "FusedLAMB"
+    _timer_kinds = (L.GS_OP_LAMB_MOMENTS, L.GS_OP_LAMB)
+    sq_norms = _sq_norms
+    _bind_adapt = _bind_adapt
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, bias_correction=True,
                  min_trust=None, max_trust=None, max_grad_norm=None, *, capturable=False):
@@ -767,18 +759,6 @@ class FusedLAMB(_DeviceSteps, _FusedBase):
         super().__init__(params, defaults)
         self._last_norms: list = []
 
-    def kernel_ms(self) -> list:
-        """Durations (ms) of the moments passes and the updates since the last call, all plans."""
-        kinds = (L.GS_OP_LAMB_MOMENTS, L.GS_OP_LAMB)
-        return [ms for plan in self._plans.plans() if plan.kind == L.GS_DEV_HIP
-                for k, v in plan.timer_read_by_kind().items() if k in kinds for ms in v]
-
-    def sq_norms(self) -> list:
-        """[(params, norms)] per plan of the last step: ``norms`` is the fp32[2n]
-        tensor the step published, [2t] = Σp² (before the update), [2t+1] = Σu²
-        of ``params[t]`` (overwritten by the next step)."""
-        return list(self._last_norms)
-
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -786,85 +766,20 @@ class FusedLAMB(_DeviceSteps, _FusedBase):
             with torch.enable_grad():
                 loss = closure()
         cap = self._device_state()  # device step counters: capturable or AMP (no host read of found_inf)
-        work = []
-        for gi, group in enumerate(self.param_groups):
-            buckets: dict = {}
-            by_cohort: dict = {}
-            h = None
-            live = []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.grad.is_sparse:
-                    raise RuntimeError("FusedLAMB does not support sparse gradients")
-                _check_dense(p, p.grad, "FusedLAMB", self._dense_seen)
-                if p.dtype != torch.float32:
-                    raise RuntimeError("FusedLAMB expects fp32 parameters (keep a fp32 master copy)")
-                st = self.state[p]
-                if "exp_avg" not in st:
-                    if _capturing():
-                        raise RuntimeError("FusedLAMB: state must exist before capture (take an eager step first)")
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                live.append(p)
-            for p in live:
-                st = self.state[p]
-                if cap:
-                    if h is None:
-                        h = self._group_hyper(gi, group, p.device)
-                    if id(st["step"]) not in h.get("cohorts", {}):
-                        self._adopt_cohorts(h, group)
-                    by_cohort.setdefault(id(st["step"]), []).append(p)
-                else:
-                    st["step"] += 1
-                    lists = buckets.setdefault((p.grad.dtype, float(st["step"].item())), ([], [], [], []))
-                    for lst, x in zip(lists, (p, p.grad, st["exp_avg"], st["exp_avg_sq"])):
-                        lst.append(x)
-            for cid, ps in by_cohort.items():
-                c = h["cohorts"][cid]
-                if len(ps) < len(c["members"]):
-                    c = self._split_cohort(h, c, ps)
-                work.append((group, None, gi, (h, c)))  # advance the cohort's counter, form its hyper source
-                for p in ps:
-                    st = self.state[p]
-                    lists = buckets.setdefault((p.grad.dtype, id(c["step"])), ([], [], [], []))
-                    for lst, x in zip(lists, (p, p.grad, st["exp_avg"], st["exp_avg_sq"])):
-                        lst.append(x)
-            cohort_hyper = {id(c["step"]): c["hyper"] for c in h["cohorts"].values()} if h is not None else {}
-            for (gdt, step), (ps, gs, ms, vs) in buckets.items():
-                plan = self._plans.get(ps)
-                plan.set_ptrs(0, ps)
-                plan.set_ptrs(1, gs)
-                plan.set_ptrs(2, ms)
-                plan.set_ptrs(3, vs)
-                adapt = group.get("adapt")
-                flags = tuple((p.ndim > 1) if adapt is None else bool(adapt) for p in ps)
-                if getattr(plan, "_adapt", None) != flags:
-                    if _capturing():
-                        raise RuntimeError("FusedLAMB: take one eager step before capturing "
-                                           "(the plan's adaptation flags and scratch are set there)")
-                    plan.set_adapt(flags)
-                    plan._adapt = flags
-                    plan._lamb_norms = torch.zeros(2 * len(ps), dtype=torch.float32, device=ps[0].device)
-                if cap:
-                    hyper = cohort_hyper[step]
-                    if getattr(plan, "_hyper", None) is not hyper:
-                        plan.set_hyper_source(hyper)
-                    step = None
-                work.append((group, plan, gdt, step, ps))
-        if not work:
-            return loss
-        if cap:
-            self.refresh_hyper()
+        work = self._gather(cap)
         plans = [(w[1], w[2]) for w in work if w[1] is not None]
         if not plans:
             return loss
-        self._last_norms = [(w[4], w[1]._lamb_norms) for w in work if w[1] is not None]
+        for group, plan, _, _, ps in work:
+            if plan is not None:
+                self._bind_adapt(plan, group, ps)
+        if cap:
+            self.refresh_hyper()
+        self._last_norms = [(w[4], w[1]._norms) for w in work if w[1] is not None]
         scale = self.grad_scale
         if self.defaults.get("max_grad_norm"):
             scale = self._clip_scale_separate(plans[0][0].device, plans)
-        for group, plan, gdt, step, *_ in work:
+        for group, plan, gdt, step, _ in work:
             beta1, beta2 = group["betas"]
             if plan is None:  # device counters: advance the cohort's step, form its hyper source
                 h, c = step
@@ -880,7 +795,7 @@ class FusedLAMB(_DeviceSteps, _FusedBase):
                 bc2s = math.sqrt(1 - beta2 ** step)
             lo = 0.0 if group["min_trust"] is None else group["min_trust"]
             hi = math.inf if group["max_trust"] is None else group["max_trust"]
-            norms = plan._lamb_norms
+            norms = plan._norms
             plan.lamb_moments(gdt, beta1, beta2, group["eps"], group["weight_decay"], bc1, bc2s, norms,
                               grad_scale=scale, found_inf=self.found_inf)
             plan.lamb(group["lr"], group["eps"], group["weight_decay"], bc1, bc2s, norms, lo, hi,

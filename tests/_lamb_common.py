@@ -14,8 +14,8 @@ import math
 import numpy as np
 import torch
 
-from tests._lars_common import (ADAPT, I_OFFSET, I_ZERO_G, I_ZERO_P, SIZES, F, assert_lists_equal,  # noqa: F401
-                                assert_sums_close, small_model, synthetic_grads, to_np)
+from tests._lars_common import (ADAPT, ADAPT2, I_OFFSET, I_ZERO_G, I_ZERO_P, SIZES, SIZES2, F,  # noqa: F401
+                                assert_lists_equal, assert_sums_close, small_model, synthetic_grads, to_np)
 
 
 def bias_corrections(beta1, beta2, step, on=True):
@@ -103,15 +103,17 @@ def _place(x, i, device):
     return x.to(device)
 
 
-def make_tensors(device, gdt, exact, seed, what="pgmv"):
-    """Lists of the tensor list drawn on the CPU from `seed`.
+def make_tensors(device, gdt, exact, seed, what="pgmv", sizes=SIZES):
+    """Lists of the tensor list drawn on the CPU from `seed` (the zero tensors and the
+    offset one are SIZES' alone).
 
     exact: p in multiples of 0.5 in [-2, 2], g in non-zero multiples of 0.5 in [-2, 2]
     (no zero-g tensor), m = v = 0.  Otherwise normal draws, v as squares (>= 0); the
     zero-g tensor has m = v = 0 too, so its update is the decay term alone."""
     gen = torch.Generator().manual_seed(seed)
     out = {k: [] for k in what}
-    for i, n in enumerate(SIZES):
+    special = sizes is SIZES
+    for i, n in enumerate(sizes):
         for k in what:
             if exact:
                 if k == "p":
@@ -125,26 +127,26 @@ def make_tensors(device, gdt, exact, seed, what="pgmv"):
                 x = torch.randn(n, generator=gen)
                 if k == "v":
                     x = x * x
-                if k in "gmv" and i == I_ZERO_G:
+                if special and k in "gmv" and i == I_ZERO_G:
                     x = torch.zeros(n)
-            if k == "p" and i == I_ZERO_P:
+            if special and k == "p" and i == I_ZERO_P:
                 x = torch.zeros(n)
-            out[k].append(_place(x.to(gdt if k == "g" else torch.float32), i, device))
+            out[k].append(_place(x.to(gdt if k == "g" else torch.float32), i if special else -1, device))
     return [out[k] for k in what]
 
 
-def make_plan(device, p, g, m, v, adapt=ADAPT):
+def make_plan(device, p, g, m, v, adapt=ADAPT, sizes=SIZES):
     from distributed_training_amd.multi_tensor import TensorListPlan
 
-    plan = TensorListPlan(SIZES, device)
+    plan = TensorListPlan(sizes, device)
     for s, ts in enumerate((p, g, m, v)):
         plan.set_ptrs(s, ts)
     plan.set_adapt(adapt)
     return plan
 
 
-def new_norms(device):
-    return torch.zeros(2 * len(SIZES), dtype=torch.float32, device=device)
+def new_norms(device, n=len(SIZES)):
+    return torch.zeros(2 * n, dtype=torch.float32, device=device)
 
 
 def plan_step(plan, gdt, norms, hp, step, mult=None, found_inf=None, lo=0.0, hi=math.inf):
@@ -167,21 +169,21 @@ def ref_plan_step(rp, rg, rm, rv, adapt, hp, step, sums=None, mult=None, lo=0.0,
 EXACT_HP = dict(lr=0.125, betas=(0.5, 0.75), eps=0.0, wd=0.5, bias_correction=True)
 
 
-def run_exact_step(device, gdt, mult=None):
+def run_exact_step(device, gdt, mult=None, sizes=SIZES, adapt=None):
     """Issue check 1: every intermediate is exact (u = ±1 + 0.5 p, u² in multiples of
     1/16, sums < 2^24/16), so Σp², Σu² equal the restatement's bit for bit whatever the
     order, and so do p, m, v.  A multiplier of 0.5 keeps everything on the grid."""
-    p, g, m, v = make_tensors(device, gdt, True, seed=31)
+    p, g, m, v = make_tensors(device, gdt, True, seed=31, sizes=sizes)
     rp, rg, rm, rv = to_np(p), to_np(g), to_np(m), to_np(v)
-    adapt = [True] * len(SIZES)
-    plan = make_plan(device, p, g, m, v, adapt)
-    norms = new_norms(device)
+    adapt = [True] * len(sizes) if adapt is None else adapt
+    plan = make_plan(device, p, g, m, v, adapt, sizes)
+    norms = new_norms(device, len(sizes))
     mt = None if mult is None else torch.tensor([mult], dtype=torch.float32, device=device)
     plan_step(plan, gdt, norms, EXACT_HP, 1, mt)
     wp, wm, wv, u, sums = ref_plan_step(rp, rg, rm, rv, adapt, EXACT_HP, 1, mult=mult)
     # the restatement's own float32 sums are exact: they equal the float64 ones
-    want64 = np.zeros(2 * len(SIZES))
-    for t in range(len(SIZES)):
+    want64 = np.zeros(2 * len(sizes))
+    for t in range(len(sizes)):
         want64[2 * t] = np.sum(rp[t].astype(np.float64) ** 2)
         want64[2 * t + 1] = np.sum(u[t].astype(np.float64) ** 2)
     assert np.array_equal(sums.astype(np.float64), want64)
@@ -191,6 +193,33 @@ def run_exact_step(device, gdt, mult=None):
     assert_lists_equal(to_np(v), wv, "v")
     assert_lists_equal(to_np(p), wp, "p")
     plan.close()
+
+
+def run_group_shapes(device, gdt):
+    """The exact-sum step on SIZES2 (tests/_lars_common.py: group shapes of the segmented
+    pass that SIZES never forms), alternating adapt flags (an unadapted tensor's u is ±1)."""
+    run_exact_step(device, gdt, sizes=SIZES2, adapt=ADAPT2)
+
+
+def run_shared_order(device, gdt):
+    """LARS's and LAMB's per-tensor passes add Σp² in one order: on random inputs and the
+    same p, gs_lars_norms and gs_lamb_moments (fresh plans) publish the same Σp² bits."""
+    from tests import _lars_common as LC
+
+    hp = dict(betas=(0.9, 0.999), eps=1e-6, wd=0.01)
+    for sizes, adapt in ((SIZES, ADAPT), (SIZES2, ADAPT2)):
+        p, g, m, v = make_tensors(device, gdt, False, seed=41, sizes=sizes)
+        lars = LC.make_plan(device, p, g, None, 0.0, sizes, adapt)
+        n_lars = new_norms(device, len(sizes))
+        lars.lars_norms(gdt, n_lars)
+        lamb = make_plan(device, p, g, m, v, adapt, sizes)
+        n_lamb = new_norms(device, len(sizes))
+        lamb.lamb_moments(gdt, *hp["betas"], hp["eps"], hp["wd"], 0.1, 0.03, n_lamb)
+        a, b = n_lars.cpu().numpy()[0::2], n_lamb.cpu().numpy()[0::2]
+        assert np.count_nonzero(a) >= len(sizes) // 2  # the passes ran
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), np.nonzero(a != b)
+        lars.close()
+        lamb.close()
 
 
 def run_random_steps(device, gdt, wd, bias_correction, steps=3):

@@ -21,6 +21,19 @@ I_OFFSET, I_ZERO_P, I_ZERO_G = len(SIZES) - 3, len(SIZES) - 2, len(SIZES) - 1
 ADAPT = [i % 2 == 0 for i in range(len(SIZES))]
 ADAPT[I_ZERO_P] = ADAPT[I_ZERO_G] = True  # the ratio-1 rule is only reached on adapted tensors
 
+# Group shapes of the segmented pass (4 chunks of 1 Ki elements per group) that SIZES never
+# forms: there the only tensor of >= 4 Ki elements behind another one starts on a group
+# boundary, so a group of 4 full chunks is always one tensor's.  By build_chunk_map
+# (gs_plan.cpp: tensors >= 4 Ki start on a multiple of 4 Ki, >= 1 Ki on a multiple of 1 Ki)
+# these start at 0, 2048, 4096, 7168, 8192, 12288, 16384:
+#   group 0  chunks 0-3    full, tensors 0 and 1
+#   group 1  chunks 4-7    full, tensors 2 and 3
+#   group 2  chunks 8-11   one full chunk (tensor 4), then three empty ones (the 4 Ki tensor's alignment gap)
+#   group 3  chunks 12-15  full (tensor 5): the fast path right before ...
+#   group 4  chunks 16-17  ... a short last group: one full chunk and tensor 6's 476-element tail
+SIZES2 = [2048, 2048, 3072, 1024, 1024, 4096, 1500]
+ADAPT2 = [i % 2 == 0 for i in range(len(SIZES2))]
+
 
 def _draw(n, exact, gen):
     if exact:  # multiples of 0.5 in [-2, 2]: every square and every partial sum is exact in fp32
@@ -28,17 +41,19 @@ def _draw(n, exact, gen):
     return torch.randn(n, generator=gen)
 
 
-def make_tensors(device, gdt, exact, seed, what="pgb"):
-    """Lists p, g (dtype gdt), b of the tensor list, drawn on the CPU from `seed`."""
+def make_tensors(device, gdt, exact, seed, what="pgb", sizes=SIZES):
+    """Lists p, g (dtype gdt), b of the tensor list, drawn on the CPU from `seed` (the
+    zero tensors and the offset one are SIZES' alone)."""
     gen = torch.Generator().manual_seed(seed)
     out = {k: [] for k in what}
-    for i, n in enumerate(SIZES):
+    special = sizes is SIZES
+    for i, n in enumerate(sizes):
         for k in what:
             x = _draw(n, exact, gen)
-            if (k == "p" and i == I_ZERO_P) or (k == "g" and i == I_ZERO_G):
+            if special and ((k == "p" and i == I_ZERO_P) or (k == "g" and i == I_ZERO_G)):
                 x = torch.zeros(n)
             x = x.to(gdt if k == "g" else torch.float32)
-            if i == I_OFFSET:
+            if special and i == I_OFFSET:
                 store = torch.zeros(n + 1, dtype=x.dtype, device=device)
                 store[1:].copy_(x)
                 x = store[1:]
@@ -121,15 +136,15 @@ def assert_sums_close(got, p, g, cols=(0, 1)):
 HYPER = dict(lr=0.1, eta=1e-3, eps=1e-8)
 
 
-def make_plan(device, p, g, b, mom):
+def make_plan(device, p, g, b, mom, sizes=SIZES, adapt=ADAPT):
     from distributed_training_amd.multi_tensor import TensorListPlan
 
-    plan = TensorListPlan(SIZES, device)
+    plan = TensorListPlan(sizes, device)
     plan.set_ptrs(0, p)
     plan.set_ptrs(1, g)
     if mom != 0:
         plan.set_ptrs(2, b)
-    plan.set_adapt(ADAPT)
+    plan.set_adapt(adapt)
     return plan
 
 
@@ -139,7 +154,7 @@ def plan_step(plan, gdt, norms, mom, wd, mult=None, found_inf=None, lr=None):
               grad_scale=mult, found_inf=found_inf)
 
 
-def run_plan_steps(device, gdt, mom, wd, mult, exact, steps=3):
+def run_plan_steps(device, gdt, mom, wd, mult, exact, steps=3, sizes=SIZES, adapt=ADAPT):
     """`steps` consecutive steps at plan level, each checked against the restatement.
 
     Exact-sum inputs: the grads of every step are fresh exact-sum draws, so Σg² is
@@ -149,14 +164,14 @@ def run_plan_steps(device, gdt, mom, wd, mult, exact, steps=3):
     computes its own sums (the whole step), later against it fed its own Σg² and
     the published Σp².  Random inputs: sums to the float64 bound, p and buf
     bit-exact against the restatement fed the published sums."""
-    p, g, b = make_tensors(device, gdt, exact, seed=11)
+    p, g, b = make_tensors(device, gdt, exact, seed=11, sizes=sizes)
     rp, rg, rb = to_np(p), to_np(g), to_np(b)
-    plan = make_plan(device, p, g, b, mom)
-    norms = torch.zeros(2 * len(SIZES), dtype=torch.float32, device=device)
+    plan = make_plan(device, p, g, b, mom, sizes, adapt)
+    norms = torch.zeros(2 * len(sizes), dtype=torch.float32, device=device)
     mt = None if mult is None else torch.tensor([mult], dtype=torch.float32, device=device)
     for s in range(steps):
         if s > 0:
-            (g2,) = make_tensors(device, gdt, exact, seed=11 + s, what="g")
+            (g2,) = make_tensors(device, gdt, exact, seed=11 + s, what="g", sizes=sizes)
             for dst, src in zip(g, g2):
                 dst.copy_(src)
             rg = to_np(g)
@@ -175,10 +190,16 @@ def run_plan_steps(device, gdt, mom, wd, mult, exact, steps=3):
         else:
             assert_sums_close(got, rp, rg)
             sums = got
-        rp, rb = ref_step(rp, rg, rb, sums, ADAPT, HYPER["lr"], mom, wd, HYPER["eta"], HYPER["eps"], mult)
+        rp, rb = ref_step(rp, rg, rb, sums, adapt, HYPER["lr"], mom, wd, HYPER["eta"], HYPER["eps"], mult)
         assert_lists_equal(to_np(p), rp, f"step {s}: p")
         assert_lists_equal(to_np(b), rb, f"step {s}: buf")
     plan.close()
+
+
+def run_group_shapes(device, gdt):
+    """One exact-sum step on SIZES2 (the group shapes above), alternating adapt flags:
+    Σp², Σg², p and buf bit for bit against the restatement."""
+    run_plan_steps(device, gdt, 0.9, 1e-4, None, True, steps=1, sizes=SIZES2, adapt=ADAPT2)
 
 
 def run_found_inf(device, gdt=torch.float32):

@@ -16,6 +16,16 @@ def test_exact_sum_step(cuda_device, gdt, mult):
     C.run_exact_step(cuda_device, gdt, mult)
 
 
+@pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])
+def test_exact_sum_step_group_shapes(cuda_device, gdt):
+    C.run_group_shapes(cuda_device, gdt)
+
+
+@pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])
+def test_lars_and_lamb_passes_share_one_order(cuda_device, gdt):
+    C.run_shared_order(cuda_device, gdt)
+
+
 @pytest.mark.parametrize("bias_correction", [True, False])
 @pytest.mark.parametrize("wd", [0.01, 0.0])
 @pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])

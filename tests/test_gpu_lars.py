@@ -19,6 +19,11 @@ def test_plan_exact_sum_inputs(cuda_device, gdt, mom, wd, mult):
     C.run_plan_steps(cuda_device, gdt, mom, wd, mult, exact=True)
 
 
+@pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])
+def test_plan_exact_sum_group_shapes(cuda_device, gdt):
+    C.run_group_shapes(cuda_device, gdt)
+
+
 @pytest.mark.parametrize("gdt,mom,wd", GRID)
 def test_plan_random_inputs(cuda_device, gdt, mom, wd):
     C.run_plan_steps(cuda_device, gdt, mom, wd, None, exact=False)

@@ -23,6 +23,15 @@ def test_exact_sum_step(gdt, mult):
     C.run_exact_step(CPU, gdt, mult)
 
 
+@pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])
+def test_exact_sum_step_group_shapes(gdt):
+    C.run_group_shapes(CPU, gdt)
+
+
+def test_lars_and_lamb_passes_share_one_order():
+    C.run_shared_order(CPU, torch.float32)
+
+
 @pytest.mark.parametrize("bias_correction", [True, False])
 @pytest.mark.parametrize("wd", [0.01, 0.0])
 @pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])

@@ -21,6 +21,11 @@ def test_plan_exact_sum_inputs(gdt, mom, wd, mult):
     C.run_plan_steps(CPU, gdt, mom, wd, mult, exact=True)
 
 
+@pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16])
+def test_plan_exact_sum_group_shapes(gdt):
+    C.run_group_shapes(CPU, gdt)
+
+
 @pytest.mark.parametrize("gdt,mom,wd", GRID)
 def test_plan_random_inputs(gdt, mom, wd):
     C.run_plan_steps(CPU, gdt, mom, wd, None, exact=False)
