@@ -134,19 +134,35 @@ def ddp_average(local_grads_per_rank, bucket_dtype="f32", align=0):
     return unpack(summed, shapes, np.float32, align)
 
 
+def _lowp_buf(lowp, n):
+    """(buffer, dtype code) of an update's low-precision copy; (None, 0) without one"""
+    if lowp is None:
+        return None, 0
+    if lowp == "bf16":
+        return np.zeros(n, dtype=np.uint16), BF16
+    if lowp == "f16":
+        return np.zeros(n, dtype=np.float16), F16
+    raise ValueError(f"lowp: None, 'bf16' or 'f16', got {lowp!r}")
+
+
 def sgd(p, g, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, maximize=False,
-        first=False, gscale=None):
+        first=False, gscale=None, lowp=None):
+    """``lowp`` ("bf16" | "f16"): also returns the 16-bit copy of the new p as one more element
+    (uint16 bf16 bit patterns / np.float16)."""
     p = np.array(p, dtype=np.float32, copy=True).reshape(-1)
     buf = np.zeros_like(p) if buf is None else np.array(buf, dtype=np.float32, copy=True).reshape(-1)
     g = np.ascontiguousarray(g).reshape(-1)
     gs = None if gscale is None else np.array([gscale], dtype=np.float32)
+    lo, ldt = _lowp_buf(lowp, p.size)
     lib().or_sgd(p.size, _ptr(p), _ptr(g), _dt(g), _ptr(buf), lr, momentum, dampening, weight_decay,
-                 int(nesterov), int(maximize), int(first), _ptr(gs), None, 0)
-    return p, buf
+                 int(nesterov), int(maximize), int(first), _ptr(gs), _ptr(lo), ldt)
+    return (p, buf) if lo is None else (p, buf, lo)
 
 
 def adam(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, adamw=False,
-         maximize=False, gscale=None):
+         maximize=False, gscale=None, lowp=None):
+    """``lowp`` ("bf16" | "f16"): also returns the 16-bit copy of the new p as one more element
+    (uint16 bf16 bit patterns / np.float16)."""
     p = np.array(p, dtype=np.float32, copy=True).reshape(-1)
     m = np.array(m, dtype=np.float32, copy=True).reshape(-1)
     v = np.array(v, dtype=np.float32, copy=True).reshape(-1)
@@ -155,9 +171,10 @@ def adam(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.
     bc2 = 1 - beta2 ** step
     step_size = (lr / bc1) * -1
     gs = None if gscale is None else np.array([gscale], dtype=np.float32)
+    lo, ldt = _lowp_buf(lowp, p.size)
     lib().or_adam(p.size, _ptr(p), _ptr(g), _dt(g), _ptr(m), _ptr(v), lr, beta1, beta2, eps, weight_decay,
-                  int(adamw), int(maximize), step_size, bc2 ** 0.5, _ptr(gs), None, 0)
-    return p, m, v
+                  int(adamw), int(maximize), step_size, bc2 ** 0.5, _ptr(gs), _ptr(lo), ldt)
+    return (p, m, v) if lo is None else (p, m, v, lo)
 
 
 def sqnorm(xs):
