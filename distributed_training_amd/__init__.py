@@ -8,13 +8,16 @@ Public surface:
   CapturedStep              the whole training step recorded into one hipGraph
   AveragedModel / ShardedAveragedModel / get_ema_multi_avg_fn / get_swa_multi_avg_fn
                             fused EMA / SWA weight averaging (torch.optim.swa_utils drop-ins)
-  compat.deepspeed / compat.colossalai   API shims for the other two trainers
+  Metrics / evaluate        distributed evaluation: exact metrics kept on the device, every dataset
+                            sample counted once, the fused inference BatchNorm forward
+  compat.deepspeed / compat.colossalai  API shims for the other two trainers
 """
 from . import _lib  # noqa: F401
 from .comm import Communicator, destroy_communicators, get_communicator  # noqa: F401
 from .ddp import DDP, DistributedDataParallel, GradBucket, compute_bucket_assignment_by_size  # noqa: F401
 from .graphs import CapturedStep  # noqa: F401
 from .ema import AveragedModel, ShardedAveragedModel, get_ema_multi_avg_fn, get_swa_multi_avg_fn  # noqa: F401
+from .evaluation import Metrics, evaluate  # noqa: F401
 from .flatten import copy_flat_to, flatten_dense_tensors, unflatten_dense_tensors  # noqa: F401
 from .multi_tensor import TensorListPlan  # noqa: F401
 from .optim import FusedAdam, FusedAdamW, FusedLAMB, FusedLARS, FusedSGD, clip_grad_norm_  # noqa: F401

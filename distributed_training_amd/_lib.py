@@ -127,6 +127,10 @@ SIGNATURES = {
     "gs_add_relu_fwd": (_c_int, [_vp, _vp, _c_i64, _vp]),
     "gs_relu_maxpool_fwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
     "gs_maxpool_bwd": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
+    "gs_bn_infer_act": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_d, _c_int, _vp, _c_i64, _c_int, _vp]),
+    "gs_bn_infer_relu_maxpool": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_d, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
+    "gs_eval_accumulate": (_c_int, [_c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _p_i32, _c_int, _c_i64,
+                                    _vp, _vp, _vp]),
     "gs_clip_coef":(_c_int, [_c_int, _vp, _c_f, _c_f, _vp, _vp, _vp]),
     "gs_unscale_check": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),
     "gs_sgd_step": (

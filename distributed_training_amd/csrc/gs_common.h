@@ -379,6 +379,28 @@ int hip_ema_hyper(int64_t* n_averaged, int mode, double decay, float* hyper, voi
 int hip_ema(gs_plan* p, int sdt, int ldt, float w, int copy, void* stream);
 int host_ema(gs_plan* p, int sdt, int ldt, float w, int copy);
 
+// ---- evaluation metrics (gs_eval_accumulate: gs_eval_kernels.hip / gs_host.cpp) ----
+// A row's result in the caller's scratch: its loss and its label's rank, or why it is not counted.
+struct EvalRow {
+  float loss;
+  int32_t code;  // >= 0: the rank (kEvalNanRow: a NaN in the row, never a hit); < 0: not counted
+};
+static_assert(sizeof(EvalRow) == 8, "EvalRow layout");
+constexpr int32_t kEvalSkip = -1;  // past n_valid, or the label is ignore_index
+constexpr int32_t kEvalBad = -2;   // the label is outside [0, K)
+constexpr int32_t kEvalNanRow = INT32_MAX;
+struct EvalTopk {
+  int32_t n;
+  int32_t k[4];
+};
+// logsumexp(z) - z_y from the row's maximum m, S = sum expf(z - m) and z_y, in fp32
+GS_HD inline float eval_loss(float m, float s, float zy) { return (m - zy) + logf(s); }
+int hip_eval_accumulate(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
+                        int64_t n_valid, const EvalTopk& topk, int64_t ignore_index, void* ws, void* acc,
+                        void* stream);
+int host_eval_accumulate(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
+                         int64_t n_valid, const EvalTopk& topk, int64_t ignore_index, void* ws, void* acc);
+
 // Deferred watchdog marks (gs_comm.cpp): a consumer plan's launch carries the mark of
 // the collectives deferred to it.  comm_mark_take: 0 = nothing to do (the
 // communicator is gone or not watching), 1 = carry *ev as the launch's stop event

@@ -540,6 +540,81 @@ int host_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const
   return GS_OK;
 }
 
+// gs_eval_accumulate on the host: the rules of include/gsync.h row by row.  The sum of the
+// exponentials is pairwise (a binary counter of finished subtrees, small ones folded first), so
+// at most ceil(log2 K) roundings lie on any path, as in the device's tree; its order differs
+// from the device's, the counts do not.
+template <int DT>
+void host_eval_rows(const void* logits, const int64_t* labels, int64_t B, int K, int64_t row_stride,
+                    int64_t n_valid, int64_t ignore_index, EvalRow* ws) {
+  for (int64_t row = 0; row < B; ++row) {
+    const int64_t y = labels[row];
+    if (row >= n_valid || y == ignore_index) {
+      ws[row] = EvalRow{0.f, kEvalSkip};
+      continue;
+    }
+    if (y < 0 || y >= K) {
+      ws[row] = EvalRow{0.f, kEvalBad};
+      continue;
+    }
+    const int64_t base = row * row_stride;
+    const float zy = ldT<DT>(logits, base + y);
+    float m = -INFINITY;
+    bool nan = false;
+    for (int j = 0; j < K; ++j) {
+      const float z = ldT<DT>(logits, base + j);
+      nan |= z != z;
+      m = z > m ? z : m;
+    }
+    if (nan) {
+      ws[row] = EvalRow{std::nanf(""), kEvalNanRow};
+      continue;
+    }
+    float acc[32];
+    int rank = 0;
+    for (int j = 0; j < K; ++j) {
+      const float z = ldT<DT>(logits, base + j);
+      float e = expf(z - m);
+      rank += (z > zy) || (z == zy && j < y);
+      int l = 0;
+      for (; static_cast<uint32_t>(j) & (1u << l); ++l) e = acc[l] + e;
+      acc[l] = e;
+    }
+    float s = 0.f;
+    bool any = false;
+    for (int l = 0; l < 31; ++l) {
+      if (static_cast<uint32_t>(K) & (1u << l)) {
+        s = any ? acc[l] + s : acc[l];
+        any = true;
+      }
+    }
+    ws[row] = EvalRow{eval_loss(m, s, zy), rank};
+  }
+}
+
+int host_eval_accumulate(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
+                         int64_t n_valid, const EvalTopk& topk, int64_t ignore_index, void* ws, void* acc) {
+  EvalRow* wp = static_cast<EvalRow*>(ws);
+  GS_HOST_FLOAT(dt, DT, host_eval_rows<DT>(logits, labels, B, K, row_stride, n_valid, ignore_index, wp));
+  int64_t* ap = static_cast<int64_t*>(acc);
+  double total = 0.0;
+  for (int64_t r = 0; r < B; ++r) {  // ascending row order
+    const EvalRow w = wp[r];
+    if (w.code >= 0) {
+      total += static_cast<double>(w.loss);
+      ap[0] += 1;
+      for (int i = 0; i < topk.n; ++i) ap[4 + i] += w.code < topk.k[i];
+    } else if (w.code == kEvalBad) {
+      ap[1] += 1;
+    }
+  }
+  double cur;
+  std::memcpy(&cur, ap + 2, 8);
+  cur = cur + total;
+  std::memcpy(ap + 2, &cur, 8);
+  return GS_OK;
+}
+
 }  // namespace gs
 
 extern "C" int gs_set_host_threads(int n) {

@@ -31,10 +31,20 @@ The fused path engages only for: CUDA, training mode, 4-D channels_last bf16
 input, fp32 affine weights, C % 8 == 0, no forward hooks on the module, the
 library loaded, and ``GSYNC_FUSED_BN`` not ``0``.  Everything else (CPU, fp32,
 eval, bf16 weights, NCHW) runs the stock modules.  ``last_path`` names the path
-the latest call took: ``"fused"`` or ``"stock"``.
+the latest call took: ``"fused"``, ``"fused_eval"`` or ``"stock"``.
+
+Evaluation: inside ``fused_eval()`` an eval-mode call that needs no gradient (grad mode
+off, or neither the input nor the parameters require grad), on a module with running
+statistics and under the conditions above, is one launch: ``gs_bn_infer_act`` reads x
+(and the identity) and writes ``relu(x * s + t + identity)`` rounded to bf16 once, s and
+t formed from the live running statistics inside the kernel; the stem is
+``gs_bn_infer_relu_maxpool`` (no un-pooled output, no indices).  The output is out of
+place; ``fork=True`` returns it twice.  Outside the context, and for every training-mode
+call inside it, nothing changes.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -57,9 +67,14 @@ def _n_partials(R: int, C: int) -> int:
 
 
 def _eligible(bn, x, relu, residual) -> bool:
+    return bn.training and _shape_eligible(bn, x, relu, residual)
+
+
+def _shape_eligible(bn, x, relu, residual) -> bool:
+    """what the training path and the evaluation path both ask of a call"""
     if os.environ.get("GSYNC_FUSED_BN", "1") == "0":
         return False
-    if not (x.is_cuda and bn.training and x.dim() == 4 and x.dtype == torch.bfloat16 and x.numel() > 0):
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and x.numel() > 0):
         return False
     w, b = bn.weight, bn.bias
     if w is None or b is None or w.dtype != torch.float32 or b.dtype != torch.float32:
@@ -72,6 +87,58 @@ def _eligible(bn, x, relu, residual) -> bool:
                                      and residual.device == x.device and residual.is_contiguous(memory_format=_CL)):
         return False
     return L.available()
+
+
+_fused_eval = False
+
+
+@contextlib.contextmanager
+def fused_eval(enabled: bool = True):
+    """Inside, an eval-mode ``bn_act`` / ``bn_relu_pool`` call that needs no gradient runs the one-pass
+    inference kernels (``gs_bn_infer_act``, ``gs_bn_infer_relu_maxpool``).  Off by default; training-mode
+    calls are not affected.  ``evaluation.evaluate`` enters it."""
+    global _fused_eval
+    prev, _fused_eval = _fused_eval, bool(enabled)
+    try:
+        yield
+    finally:
+        _fused_eval = prev
+
+
+def _eval_eligible(bn, x, relu, residual) -> bool:
+    if not _fused_eval or bn.training:
+        return False
+    rm, rv = bn.running_mean, bn.running_var
+    if rm is None or rv is None or rm.dtype != torch.float32 or rv.dtype != torch.float32:
+        return False  # no running statistics: an eval-mode call normalises with the batch's
+    if not _shape_eligible(bn, x, relu, residual):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad
+                                    or (residual is not None and residual.requires_grad)):
+        return False  # the inference kernels have no backward
+    ptrs = [x.data_ptr(), rm.data_ptr(), rv.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr()]
+    if residual is not None:
+        ptrs.append(residual.data_ptr())
+    return all(p % 16 == 0 for p in ptrs)
+
+
+def _infer_act(bn, x, relu, residual):
+    y = torch.empty_like(x)  # out of place: x may be another consumer's input
+    C = x.shape[1]
+    L.check(L.lib().gs_bn_infer_act(x.data_ptr(), None if residual is None else residual.data_ptr(),
+                                    bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.weight.data_ptr(),
+                                    bn.bias.data_ptr(), bn.eps, int(bool(relu)), y.data_ptr(), x.numel() // C, C,
+                                    L.stream_ptr(x.device)), "gs_bn_infer_act")
+    return y
+
+
+def _infer_relu_pool(bn, x):
+    N, C, H, W = x.shape
+    out = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device, memory_format=_CL)
+    L.check(L.lib().gs_bn_infer_relu_maxpool(x.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                                             bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps, out.data_ptr(), N, H,
+                                             W, C, L.stream_ptr(x.device)), "gs_bn_infer_relu_maxpool")
+    return out
 
 
 class _BnAct(torch.autograd.Function):
@@ -216,6 +283,10 @@ def bn_relu_pool(bn, x, pool, fork: bool = True):
     one launch from those bytes and the one or two pooled gradients to the BatchNorm backward's dy.
     Anything else is the stock ``pool(bn_act(bn, x))``."""
     global last_path
+    if _pool_eligible(pool) and _eval_eligible(bn, x, True, None):
+        last_path = "fused_eval"
+        out = _infer_relu_pool(bn, x)
+        return (out, out) if fork else out
     if _pool_eligible(pool) and _eligible(bn, x, True, None):
         momentum = _bookkeeping(bn)
         last_path = "fused"
@@ -232,6 +303,10 @@ def bn_act(bn, x, relu: bool = True, residual=None, fork: bool = False):
     tensors alias one storage and their gradients are summed inside the BatchNorm backward's first
     pass; on the stock path it is the same tensor twice and autograd sums as ever."""
     global last_path
+    if _eval_eligible(bn, x, relu, residual):
+        last_path = "fused_eval"
+        out = _infer_act(bn, x, relu, residual)
+        return (out, out) if fork else out
     if _eligible(bn, x, relu, residual):
         momentum = _bookkeeping(bn)
         last_path = "fused"

@@ -10,6 +10,9 @@ same shape is used.
 
     torchrun --nproc-per-node 2 --master-addr 127.0.0.1 examples/ddp_train.py        # one GPU per rank (RCCL)
     python examples/ddp_train.py --device cpu --world-size 2                            # CPU / gloo (config 1)
+
+``--eval`` evaluates on the test set after every epoch (``distributed_training_amd.evaluate``: every test
+sample counted once across the ranks) and prints one line on rank 0.
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from distributed_training_amd import DDP, FusedAdam as Adam  # noqa: E402
+from distributed_training_amd import DDP, FusedAdam as Adam, evaluate  # noqa: E402
 from distributed_training_amd import data as D  # noqa: E402
 from distributed_training_amd.resnet import MODELS  # noqa: E402
 
@@ -57,8 +60,9 @@ def train_epoch(epoch, num_epochs, model, optimizer, criterion, train_dataloader
 
 
 def ddp(rank, world_size, num_epochs, learning_rate, batch_size, device_type="cuda", max_steps=None,
-        synthetic_n=50000, port=12355, result=None, local_rank=None):
-    """R:ddp_train.py:94-105 (ddp_setup :79-85 with the backend chosen by device)."""
+        synthetic_n=50000, port=12355, result=None, local_rank=None, run_eval=False):
+    """R:ddp_train.py:94-105 (ddp_setup :79-85 with the backend chosen by device).  ``run_eval``: after each
+    epoch, evaluate on the test loader the reference builds and never drains (:47)."""
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", str(port))
     if device_type == "cuda":
@@ -70,7 +74,7 @@ def ddp(rank, world_size, num_epochs, learning_rate, batch_size, device_type="cu
         dist.init_process_group("gloo", rank=rank, world_size=world_size)
     torch.manual_seed(0)
     model = DDP(MODELS["resnet18"](num_classes=10).to(device))
-    train_dataloader, _ = build_dataloader(batch_size, device, synthetic_n)
+    train_dataloader, test_dataloader = build_dataloader(batch_size, device, synthetic_n)
     optimizer = Adam(model.parameters(), lr=learning_rate)
     criterion = nn.CrossEntropyLoss()
     last = None
@@ -79,6 +83,11 @@ def ddp(rank, world_size, num_epochs, learning_rate, batch_size, device_type="cu
         last = train_epoch(epoch, num_epochs, model, optimizer, criterion, train_dataloader, max_steps)
         if rank == 0:
             print(f"epoch {epoch + 1}/{num_epochs} loss {last:.4f}", flush=True)
+        if run_eval:
+            m = evaluate(model, test_dataloader, max_batches=max_steps)
+            if rank == 0:
+                print(f"epoch {epoch + 1}/{num_epochs} eval n {m['n']} loss {m['loss']:.4f} "
+                      f"top1 {m['top1']:.4f} top5 {m['top5']:.4f}", flush=True)
     if result is not None and rank == 0:
         result.put({k: v.detach().cpu().numpy().copy() for k, v in model.module.state_dict().items()})
     dist.destroy_process_group()
@@ -92,14 +101,16 @@ def main():
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batch-size", type=int, default=100)
     ap.add_argument("--max-steps", type=int, default=None)
+    ap.add_argument("--eval", action="store_true", help="evaluate on the test set after each epoch")
     a = ap.parse_args()
     if "RANK" in os.environ:  # torchrun
         ws = int(os.environ["WORLD_SIZE"])
         ddp(int(os.environ["RANK"]), ws, a.epochs, 1e-3 * ws, a.batch_size, a.device, a.max_steps,
-            local_rank=int(os.environ.get("LOCAL_RANK", "0")))
+            local_rank=int(os.environ.get("LOCAL_RANK", "0")), run_eval=a.eval)
     else:
         ws = a.world_size
-        mp.spawn(ddp, args=(ws, a.epochs, 1e-3 * ws, a.batch_size, a.device, a.max_steps), nprocs=ws)
+        mp.spawn(ddp, args=(ws, a.epochs, 1e-3 * ws, a.batch_size, a.device, a.max_steps, 50000, 12355, None, None,
+                            a.eval), nprocs=ws)
 
 
 if __name__ == "__main__":

@@ -759,6 +759,70 @@ int gs_relu_maxpool_fwd(const void* y, void* pooled, void* idx, int64_t N, int H
 int gs_maxpool_bwd(const void* d_a, const void* d_b, const void* idx, void* dx, int64_t N, int H, int W, int C,
                    void* stream);
 
+/* ======================================================================
+ * Evaluation: inference BatchNorm fused with its tail, and exact metrics
+ * (csrc/gs_bn_kernels.hip, csrc/gs_eval_kernels.hip; Python: fused_bn.fused_eval,
+ * distributed_training_amd/evaluation.py)
+ * replaces: of an eval-mode forward, miopen_batch_norm (inference) + add_ + relu_
+ *           per residual block and relu_ + max_pool2d_with_indices in the stem;
+ *           of a validation loop, F.cross_entropy + topk + eq + sum + .item()
+ *           per batch (the reference builds its test_dataloader and never drains it:
+ *           R:resnet/pytorch_ddp/ddp_train.py:47, R:resnet/colossalai/colossal_train.py:77)
+ * ==================================================================== */
+/* y = relu(bn(x) + residual) for a BatchNorm in evaluation, where it is a per-channel
+ * affine map of its running statistics: one pass, x (and the residual) in, y out.
+ * x, residual (nullable), y: NHWC bf16 [R, C], C % 8 == 0; running_mean, running_var,
+ * weight, bias: fp32 [C]; every pointer 16-byte aligned.  y may be x (in place);
+ * otherwise y overlaps neither x nor the residual.  relu != 0 applies the ReLU.
+ * Arithmetic, all fp32, in this order (a restatement is exact op for op):
+ *   s_c = weight_c * (1.0f / sqrtf(var_c + (float)eps))     sqrt and / correctly rounded
+ *   t_c = fmaf(-mean_c, s_c, bias_c)
+ *   v   = fmaf(x, s_c, t_c);  residual: v = v + r;  relu: v = v > 0 ? v : (v is NaN ? v : +0)
+ *   y   = bf16(v), round to nearest even, once (a NaN becomes 0x7FC0); no intermediate bf16
+ * The statistics are read when the kernel runs and nothing else is touched: no folded
+ * weights to refresh after a training step.  HIP only, one launch on `stream`, no
+ * allocation, no host synchronisation, capturable.  GS_EINVAL before the launch: a null
+ * or misaligned pointer, R <= 0, C <= 0 or C % 8 != 0, eps < 0 or NaN, a forbidden overlap. */
+int gs_bn_infer_act(const void* x, const void* residual, const float* running_mean, const float* running_var,
+                    const float* weight, const float* bias, double eps, int relu, void* y, int64_t R, int C,
+                    void* stream);
+/* the stem in evaluation, one launch: pooled = MaxPool2d(3, stride 2, padding 1) over
+ * bf16(relu(fmaf(x, s_c, t_c))), s and t as above; x NHWC bf16 [N, H, W, C], pooled
+ * [N, OH, OW, C] (OH, OW as gs_relu_maxpool_fwd).  No un-pooled output and no indices are
+ * written.  Window clipping, scan order and the NaN rule are gs_relu_maxpool_fwd's, and
+ * rounding is monotonic, so pooled is bit for bit the pool of gs_bn_infer_act's output.
+ * pooled does not overlap x. */
+int gs_bn_infer_relu_maxpool(const void* x, const float* running_mean, const float* running_var, const float* weight,
+                             const float* bias, double eps, void* pooled, int64_t N, int H, int W, int C,
+                             void* stream);
+/* Adds one batch to an evaluation's accumulator.  logits: [B, K] (logits_dtype GS_F32,
+ * GS_BF16 or GS_F16), row r at logits + r * row_stride elements (row_stride >= K);
+ * labels: int64 [B]; topk: n_topk <= 4 values k >= 1 in host memory; ws: scratch of
+ * 8 * B bytes; acc: eight 8-byte words, zeroed by the caller before the first batch:
+ *   [0] rows counted (int64)        [1] rows whose label is outside [0, K) and is not
+ *   [2] sum of the losses (double)      ignore_index (int64): they count nowhere else
+ *   [3] reserved                    [4 + i] rows correct at topk[i] (int64)
+ * logits, labels, ws and acc live where device_kind says.  Rows >= n_valid (the padding
+ * a DistributedSampler appends) and rows whose label is ignore_index are skipped.  For
+ * every other row, with z the row converted to fp32 and y its label:
+ *   m = max z;  S = sum_j expf(z_j - m) (fp32, a balanced tree: at most ceil(log2 K)
+ *   roundings on a path);  loss = (m - z_y) + logf(S)
+ *   rank = #{j : z_j > z_y} + #{j < y : z_j == z_y}   (ties go to the lower index)
+ *   correct at k iff rank < k
+ * A row that holds a NaN is correct for no k and adds a NaN to the loss sum.  The call's
+ * losses are added in ascending row order in fp64 and the total is added to acc[2]; the
+ * counts are exact integers.  Bitwise repeatable: no floating-point atomics.  GS_DEV_HIP:
+ * two launches on `stream` (one wavefront per row, then one workgroup that folds the
+ * rows), no allocation, no host synchronisation, capturable.  GS_DEV_HOST: the same
+ * rules; the tree of S has the same depth but another order, so a loss may differ from
+ * the device's by a few fp32 ulps while every count is the same.
+ * GS_EINVAL before any launch: an unknown device kind or dtype, B < 0, K outside
+ * [1, 2^30], row_stride < K, n_valid outside [0, B], n_topk outside [0, 4], a k < 1,
+ * a null or misaligned pointer.  B == 0 is a no-op. */
+int gs_eval_accumulate(int device_kind, const void* logits, int logits_dtype, const int64_t* labels, int64_t B,
+                       int64_t K, int64_t row_stride, int64_t n_valid, const int32_t* topk, int n_topk,
+                       int64_t ignore_index, void* ws, void* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
