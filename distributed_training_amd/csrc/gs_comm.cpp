@@ -362,7 +362,7 @@ int comm_enqueue(gs_comm* c, hipStream_t stream, const std::function<ncclResult_
   c->enq_since.store(0);
   if (r != ncclSuccess) return rccl_fail(r, what);
   if (!track) return GS_OK;
-  if (consumer && consumer->kind == GS_DEV_HIP && consumer->n > 0 && !consumer->segs.empty() &&
+  if (consumer && consumer->kind == GS_DEV_HIP && consumer->elems > 0 &&
       c->timeout_ms > 0 && !stream_capturing(stream)) {
     consumer->watch_comm = c;
     c->deferred.push_back({consumer, stream, std::chrono::steady_clock::now()});

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/gsync.h"
+#include "gs_math.h"
 
 namespace gs {
 
@@ -58,19 +59,13 @@ inline int dtype_size(int dt) {
 }
 inline bool is_float_dtype(int dt) { return dt == GS_F32 || dt == GS_BF16 || dt == GS_F16; }
 
-// ---- multi-tensor work decomposition ----
-// A tensor is cut into segments of <= task_units units (1 unit = 4 elements;
-// plan_task_units() sizes them per plan, at most kSegUnits).
-// Consecutive segments are grouped into tasks of <= task_units units and
-// <= kMaxSegPerTask segments; one workgroup processes one task at a time
-// (small tensors share a task; their descriptors are staged in LDS).
+// ---- engine constants ----
+// 1 unit = 4 elements: one 16-B fp32 access of a lane.  The streaming kernels walk the
+// chunk map below; the plan's task decomposition (gs_plan_n_tasks / gs_plan_task_units)
+// is public metadata that gs_plan.cpp counts and no kernel reads.
 constexpr int kUnit = 4;
-constexpr int kSegUnits = 4096;   // max task: 16Ki elements = 64 KiB fp32 per stream
-constexpr int kMinTaskUnits = 256;        // one unit per lane of a 256-thread workgroup
-constexpr int kTargetTasks = 1920;  // < 2048 resident: ragged tensor ends add tasks
-constexpr int kMaxSegPerTask = 64;
 constexpr int kBlock = 256;         // 4 waves of 64
-// default grid: one workgroup per task up to kGridLimit (the dispatcher refills
+// default grid: one workgroup per group of chunks up to kGridLimit (the dispatcher refills
 // CUs faster than a resident grid loops: profiles/r1r_copy_micro.jsonl,
 // r1r_grid_sweep.jsonl)
 constexpr int kMaxGrid = 65536;
@@ -79,15 +74,6 @@ constexpr int kGridLimit = 65536;   // hard cap (partials buffer)
 // folding wave), each counter / group sum on its own 128-B line
 constexpr int kRedMaxGroups = GS_RED_GROUPS;
 constexpr int kRedSyncStride = 32;
-
-struct Seg {
-  int64_t unit_begin;  // first unit inside the tensor (interleaved part: the part index)
-  int32_t tensor;
-  int32_t units;       // (interleaved part: the tensor's units)
-  int32_t task_off;    // unit offset of this segment inside its task
-  int32_t pad;         // 0 = contiguous segment; M > 0 = one of M interleaved parts
-};
-static_assert(sizeof(Seg) == 24, "Seg layout");
 
 // ---- chunk-map engine (streaming ops) ----
 // The plan's tensors are laid end to end in a VIRTUAL element space (voff):
@@ -111,8 +97,6 @@ static_assert(sizeof(ChunkDesc) == 8, "ChunkDesc layout");
 
 // Arguments handed to a device kernel (by value).
 struct PlanArgs {
-  const Seg* segs;
-  const int32_t* task_begin;  // [n_tasks + 1]
   const int64_t* numel;       // [n]
   const int64_t* off;         // [n] flat offsets (elements)
   void* const* ptrs;          // [GS_PLAN_SLOTS * n]
@@ -126,114 +110,26 @@ struct PlanArgs {
   int32_t red_groups_only;    // stop after the group level: the R group sums stay for a clipped update
   int32_t red_raw;            // one partial per workgroup straight to red_out (no counters, no combine)
   int32_t n;
-  int32_t n_tasks;
   int32_t n_chunks;
 };
 
-// optimizer hyper-parameters, rounded to fp32 where torch rounds them
-struct SgdHyper {
-  float lr, mom, omd, wd;  // omd = float(1 - dampening) formed in double
-  int nesterov, maximize, first;
-};
-struct AdamHyper {
-  float b2, w1, w2, eps, wd, step_size, bc2s, decay;  // w1 = float(1-b1), decay = float(1-lr*wd)
-  int adamw, maximize;
-};
-// LARS (gs_lars_step): eta = the trust coefficient
-struct LarsHyper {
-  float lr, mom, wd, eta, eps;
-};
-// The per-tensor learning rate and weight decay of LARS from the tensor's Σp², Σg²
-// (include/gsync.h, gs_lars_step): every multiply and add rounded once, no fma; the
-// same expression on the host and the device (IEEE sqrt and division on both).
-// m: the grad multiplier (has_m), which scales ‖g‖ as it scales every g.
-#ifdef __HIPCC__
-#define GS_HD_INL __host__ __device__ inline
-#else
-#define GS_HD_INL inline
-#endif
-GS_HD_INL void lars_coef(const LarsHyper& h, float sp, float sg, int adapt, bool has_m, float m, float* slr,
-                         float* wd) {
-  float ratio = 1.f;
-  *wd = 0.f;
-  if (adapt != 0) {
-    *wd = h.wd;
-    const float wn = sqrtf(sp);
-    float gn = sqrtf(sg);
-    if (has_m) gn = gn * m;
-    if (wn > 0.f && gn > 0.f) ratio = (h.eta * wn) / ((gn + h.wd * wn) + h.eps);
+// One instantiation per dtype: NAME is a constexpr GS_* dtype inside the body.  For use
+// in functions of namespace gs that return an int status.
+#define GS_DISPATCH_FLOAT(DT, NAME, ...)                                \
+  switch (DT) {                                                         \
+    case GS_F32: { constexpr int NAME = GS_F32; __VA_ARGS__; break; }   \
+    case GS_BF16: { constexpr int NAME = GS_BF16; __VA_ARGS__; break; } \
+    case GS_F16: { constexpr int NAME = GS_F16; __VA_ARGS__; break; }   \
+    default: return fail(GS_EINVAL, "unsupported floating dtype");      \
   }
-  *slr = h.lr * ratio;
-}
-// LAMB (gs_lamb_moments / gs_lamb_step): w1 = float(1-b1), w2 = float(1-b2), bc2s = float(sqrt(1-b2^step));
-// lo, hi = the trust-ratio clamp (0, +inf: none)
-struct LambHyper {
-  float b1, b2, w1, w2, bc1, bc2s, eps, wd, lr, lo, hi;
-};
-// LAMB's update direction of one element from (p, m', v') (include/gsync.h, gs_lamb_moments):
-// the moments pass sums its square and the update pass recomputes it from the stored
-// moments, so both compile this one text (as does the host backend) and the recomputed
-// value is the summed one bit for bit.  Every operation rounded once, no fma.
-GS_HD_INL float lamb_update(const LambHyper& h, float p, float m, float v, float wd_t) {
-  float u = (m / h.bc1) / (sqrtf(v) / h.bc2s + h.eps);
-  if (wd_t != 0.f) u = u + wd_t * p;
-  return u;
-}
-// ... and the moments themselves: g is already multiplied
-GS_HD_INL void lamb_moments(const LambHyper& h, float g, float* m, float* v) {
-  *m = *m * h.b1 + h.w1 * g;
-  *v = *v * h.b2 + (h.w2 * g) * g;
-}
-// The per-tensor learning rate of LAMB from the tensor's Σp², Σu² (gs_lamb_step)
-GS_HD_INL float lamb_coef(const LambHyper& h, float sp, float su, int adapt) {
-  float ratio = 1.f;
-  if (adapt != 0) {
-    const float wn = sqrtf(sp), un = sqrtf(su);
-    if (wn > 0.f && un > 0.f) {
-      ratio = wn / un;
-      if (ratio < h.lo) ratio = h.lo;
-      if (ratio > h.hi) ratio = h.hi;
-    }
+// ... and the optional low-precision copy: -1 = none
+#define GS_DISPATCH_LOWP(DT, NAME, ...)                                  \
+  switch (DT) {                                                          \
+    case -1: { constexpr int NAME = -1; __VA_ARGS__; break; }            \
+    case GS_BF16: { constexpr int NAME = GS_BF16; __VA_ARGS__; break; }  \
+    case GS_F16: { constexpr int NAME = GS_F16; __VA_ARGS__; break; }    \
+    default: return fail(GS_EINVAL, "unsupported low-precision dtype");  \
   }
-  return h.lr * ratio;
-}
-inline LambHyper make_lamb(double b1, double b2, double bc1, double bc2s, double eps, double wd, double lr, double lo,
-                           double hi) {
-  return LambHyper{static_cast<float>(b1), static_cast<float>(b2), static_cast<float>(1.0 - b1),
-                   static_cast<float>(1.0 - b2), static_cast<float>(bc1), static_cast<float>(bc2s),
-                   static_cast<float>(eps), static_cast<float>(wd), static_cast<float>(lr),
-                   static_cast<float>(lo), static_cast<float>(hi)};
-}
-// Gradient-norm clip folded into an update launch (gs_plan_set_clip): the
-// update's workgroups form the coefficient themselves, so no coefficient
-// launch (and, with the plan's own group sums, no combine launch) sits between
-// the Σg² kernel and the update.  Same arithmetic as the separate path
-// (sq *= gscale², sq *= sq_mul; norm = sqrt(sq); coef = min(1, max/(norm+eps))
-// * gscale * coef_mul, T:nn/utils/clip_grad.py:165-174), so it is bit-identical.
-struct ClipArgs {
-  const float* sq;     // a finished Σg² (groups == 0) or `groups` group sums, `stride` floats apart
-  int32_t groups;
-  int32_t stride;      // floats between consecutive group sums (1: contiguous; the plan's own copy and a caller's buffer)
-  float max_norm, eps;
-  float sq_mul, coef_mul;  // host multipliers (ZeRO's loss scale): 1 = none
-  float* out;          // [sq, coef, norm] written by workgroup 0 (nullable)
-  // 0: DeepSpeed's `if coef < 1: clip` (a NaN coefficient clips nothing); 1: torch's
-  // clamp(coef, max=1) (clip_grad_norm_, T:nn/utils/clip_grad.py:172 — NaN stays NaN)
-  int32_t torch_clamp;
-};
-
-inline SgdHyper make_sgd(double lr, double mom, double damp, double wd, int nest, int maxi,
-                         int first) {
-  return SgdHyper{static_cast<float>(lr), static_cast<float>(mom),
-                  static_cast<float>(1.0 - damp), static_cast<float>(wd), nest, maxi, first};
-}
-inline AdamHyper make_adam(double lr, double b1, double b2, double eps, double wd, int adamw,
-                           int maxi, double step_size, double bc2s) {
-  return AdamHyper{static_cast<float>(b2), static_cast<float>(1.0 - b1),
-                   static_cast<float>(1.0 - b2), static_cast<float>(eps),
-                   static_cast<float>(wd), static_cast<float>(step_size),
-                   static_cast<float>(bc2s), static_cast<float>(1.0 - lr * wd), adamw, maxi};
-}
 
 }  // namespace gs
 
@@ -246,19 +142,18 @@ struct gs_plan {
   int64_t flat_numel = 0;
   int64_t elems = 0;                   // Σ numel (the load policy's stream sizes)
   std::vector<int64_t> numel, off;
-  std::vector<gs::Seg> segs;
-  std::vector<int32_t> task_begin;
   std::vector<int64_t> voff;           // chunk-map engine: virtual offsets
   std::vector<gs::ChunkDesc> chunks;   // chunk-map engine: one per kChunkElems elements of voff space
-  int grid = 0;
   int grid_cap = gs::kMaxGrid;         // the streaming ops' grid cap
+  // the public work decomposition (gs_plan_task_units / gs_plan_n_tasks): reported, not acted on
   int64_t task_units = 0;
+  int n_tasks = 0;
   // host shadow of the pointer table
   std::vector<void*> h_ptrs;       // [SLOTS * n]
   std::vector<uint32_t> h_align;   // [n]
   bool dirty = true;
   // device side (HIP plans only)
-  void* d_static = nullptr;  // segs | task_begin | numel | off | chunks | voff
+  void* d_static = nullptr;  // numel | off | chunks | voff
   void* d_table = nullptr;   // ptrs | align
   float* d_partials = nullptr;  // [kGridLimit] partials + the fused reduction's sync words
   void* pinned = nullptr;       // staging ring for table uploads

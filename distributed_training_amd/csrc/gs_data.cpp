@@ -97,13 +97,6 @@ void store_torch_state(const Mt19937& m, uint8_t* st) {
   }
 }
 
-inline uint16_t f32_to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7FC0;
-  return static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
 int host_image_augment(const ImageAugArgs& a) {
   const int64_t per = static_cast<int64_t>(a.C) * a.out_h * a.out_w;
   for (int64_t b = 0; b < a.B; ++b) {

@@ -1,7 +1,9 @@
-// The gfx950 streaming engine of libgsync, shared by the kernel translation units
-// (gs_kernels.hip: pack / unpack / reductions / plan memory; gs_update_kernels.hip:
-// the fused SGD / Adam updates — two TUs so hipcc compiles them in parallel).
-// Device code: include from .hip sources only.
+// The gfx950 streaming engine of libgsync, shared by the two kernel translation units
+// that run plan ops (gs_kernels.hip: pack / unpack / reductions / plan memory;
+// gs_update_kernels.hip: the fused SGD / Adam / LARS / LAMB updates and the EMA average —
+// two TUs so hipcc compiles them in parallel).  The other three .hip files
+// (gs_data_kernels, gs_bn_kernels, gs_eval_kernels) have kernels of their own and do not
+// use it.  Device code: include from .hip sources only.
 //
 // All of them are HBM-streaming kernels (no MFMA: nothing here is a
 // contraction).  One engine serves every op (chunk_kernel): a plan lays its
@@ -12,9 +14,10 @@
 // chunks where tensors meet (tensor tails, runs of BN weights / biases) stage
 // the span's descriptors in LDS and resolve each lane's tensor there.
 //
-// Arithmetic is written with explicit fmaf and compiled with
-// -ffp-contract=off so that the host restatement (oracle/gs_oracle.c) and
-// the host backend (gs_host.cpp) reproduce it bit for bit.
+// The update arithmetic and the dtype conversions are gs_math.h's, the texts the host
+// backend (gs_host.cpp) compiles too; fused multiply-adds are explicit fmaf and the build
+// sets -ffp-contract=off, so the independent restatement (oracle/gs_oracle.c) reproduces
+// them bit for bit.
 
 #pragma once
 
@@ -41,50 +44,7 @@ namespace {
   } while (0)
 
 // ---------------------------------------------------------------- dtype I/O
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) {
-  return __uint_as_float(static_cast<uint32_t>(h) << 16);
-}
-// round-to-nearest-even; NaN -> 0x7FC0 (c10::BFloat16 round_to_nearest_even)
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7FC0;
-  return static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float f16_to_f32(uint16_t h) {
-  _Float16 x;
-  __builtin_memcpy(&x, &h, 2);
-  return static_cast<float>(x);
-}
-// fp32 -> fp16, round-to-nearest-even of the fp32 VALUE (torch: opmath in fp32,
-// then the cast).  The empty asm pins f as an fp32 register value: without it
-// LLVM folds the producing fma / mul into v_fma_mixlo_f16, which rounds the
-// exact result once, straight to fp16 — a different fp16 wherever the fp32
-// rounding lands on an fp16 tie (ZeRO fp16 params, fp16 buckets, fp16 unscale;
-// found as master.half() != the fp16 param in test_colossal_low_level_zero_fp16_gpu)
-__device__ __forceinline__ uint16_t f32_to_f16(float f) {
-  __asm__("" : "+v"(f));
-  _Float16 x = static_cast<_Float16>(f);
-  uint16_t h;
-  __builtin_memcpy(&h, &x, 2);
-  return h;
-}
-
-template <int DT>
-__device__ __forceinline__ float to_f32(uint16_t h) {
-  if constexpr (DT == GS_BF16) return bf16_to_f32(h);
-  else return f16_to_f32(h);
-}
-template <int DT>
-__device__ __forceinline__ uint16_t from_f32(float f) {
-  if constexpr (DT == GS_BF16) return f32_to_bf16(f);
-  else return f32_to_f16(f);
-}
-// value as it would read back after a store in DT (used for norms / casts)
-template <int DT>
-__device__ __forceinline__ float round_to(float f) {
-  if constexpr (DT == GS_F32) return f;
-  else return to_f32<DT>(from_f32<DT>(f));
-}
+// (conversions: gs_math.h)
 
 // Plan pointers are read from a table, so the compiler only sees generic
 // pointers and would emit flat_* accesses; every buffer here is device
@@ -389,9 +349,9 @@ __device__ __forceinline__ float block_reduce(float v) {
 }
 
 // ------------------------------------------------------------- the engine
-// Everything a unit needs about its tensor, staged once per task in LDS
-// (one entry per segment of the task) instead of re-read from the global
-// tables for every unit.
+// Everything a lane-access needs about its tensor (load_tv): read once per group of
+// full chunks through scalar loads, or, for a mixed chunk, staged once per chunk in LDS
+// (one entry per tensor of the span, chunk_mixed_lds).
 struct TV {
   void* ptr[GS_PLAN_SLOTS];
   int64_t numel;
@@ -405,18 +365,39 @@ struct TV {
 //   struct Frag;                             registers for one unit (4 elements)
 //   load_hyper(Op&) overload (optional)      step-varying hyper-parameters from device memory
 //   bool active() const;                     uniform early-out (found_inf skip)
+//   int phys(int k) const;                   table row of logical slot k (load_tv)
 //   void load(const TV&, e, Frag&)           issue the unit's loads
 //   void apply(const TV&, e, Frag&, acc)     compute + store (+ reduction)
 //   static constexpr int kRed = 0 (none) | 1 (sum) | 2 (max); float* partials
 //   static constexpr int kKind = GS_OP_* (tags the launch timer's records)
+// OpBase below holds the defaults.
 // default: hyper-parameters travel in the kernel arguments
 template <class Op>
 __device__ __forceinline__ void load_hyper(Op&) {}
+// What most ops share; an op states only what differs (kG, kKind, its members, and
+// whichever of these it overrides).  `partials` is the first kernel-argument word of every op.
+template <int N>
+struct OpBase {
+  static constexpr int kN = N;
+  static constexpr int kRed = 0;
+  static constexpr int kRedGrid = kGridLimit;
+  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
+  float* partials = nullptr;
+  __device__ int phys(int k) const { return k; }
+  __device__ bool active() const { return true; }
+};
+// ... of an op that addresses one runtime slot: logical slot 0 = table row `slot`
+// (descriptor loads, load_tv)
+template <int N>
+struct SlotOpBase : OpBase<N> {
+  int slot;
+  __device__ int phys(int k) const { return k == 0 ? slot : k; }
+};
 
 // The plan tables are read-only for the whole launch: reading them through
-// the constant address space lets the uniform descriptor loads of a
-// single-segment task go to the scalar unit (s_load), with no LDS round trip
-// and no barrier before the first data load.
+// the constant address space lets the uniform descriptor loads of a group of
+// full chunks go to the scalar unit (s_load), with no LDS round trip and no
+// barrier before the first data load.
 #define CONST_AS __attribute__((address_space(4)))
 template <class T>
 __device__ __forceinline__ T cload(const T* p, int64_t i) {
@@ -742,22 +723,13 @@ __device__ __forceinline__ char* flat_at(void* flat, int64_t off) {
 // NT: non-temporal loads of the source (a read-once stream above the cache size, nt_read_once)
 // G2: a small plan into an fp32 bucket takes groups of 2 chunks (pack_group_small)
 template <int N, int SD, int FD, int MODE, bool NT = false, bool G2 = false>
-struct PackOp {
-  static constexpr int kN = N;
+struct PackOp : SlotOpBase<N> {
   static constexpr int kG = FD == GS_F32 ? (G2 ? 2 : GS_G_PACK) : (SD == GS_F32 ? GS_G_PACK16 : GS_G_PACK16_16);
-  static constexpr int kRed = 0;
-  static constexpr int kRedGrid = kGridLimit;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_PACK;
-  float* partials = nullptr;
-  int slot;
   void* flat;
   bool flat_vec;
   float s;
   struct Frag { float x[N]; };
-  // logical slot 0 = the op's table row `slot` (descriptor loads, gs_kernels.hip: load_tv)
-  __device__ int phys(int k) const { return k == 0 ? slot : k; }
-  __device__ bool active() const { return true; }
   __device__ bool fast_ok(const TV& v) const {
     return flat_vec && (v.off % 4) == 0 && (v.ptr[0] == nullptr || v.vec(0));
   }
@@ -791,22 +763,18 @@ struct PackOp {
 // flag of the written values (fused AMP inf check, max-combined into the flag)
 // NT: non-temporal loads of the flat buffer (above the cache size, nt_read_once)
 template <int N, int FD, int DD, int RED = 1, bool NT = false>
-struct UnpackOp {
-  static constexpr int kN = N;
+struct UnpackOp : OpBase<N> {
   static constexpr int kG = GS_G_UNPACK;
   static constexpr int kRed = RED;
-  static constexpr int kRedGrid = kGridLimit;
   static constexpr int kRedFuseGrid = 8192;  // its fused Σg² / inf check: <= 2 groups per workgroup (r4l)
   static constexpr int kKind = GS_OP_UNPACK;
-  float* partials = nullptr;
   bool want_red;
   const void* flat;
   bool flat_vec;
   int slot;
   struct Frag { float x[N]; };
-  // logical slot 0 = the op's table row `slot` (descriptor loads, gs_kernels.hip: load_tv)
+  // SlotOpBase's mapping (`slot` sits behind the flat buffer here)
   __device__ int phys(int k) const { return k == 0 ? slot : k; }
-  __device__ bool active() const { return true; }
   __device__ bool fast_ok(const TV& v) const {
     return flat_vec && (v.off % 4) == 0 && (v.ptr[0] == nullptr || v.vec(0));
   }
@@ -832,21 +800,12 @@ struct UnpackOp {
 };
 
 template <int N, int DT>
-struct ScaleOp {
-  static constexpr int kN = N;
+struct ScaleOp : SlotOpBase<N> {
   static constexpr int kG = GS_G_UNPACK;
-  static constexpr int kRed = 0;
-  static constexpr int kRedGrid = kGridLimit;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_SCALE;
-  float* partials = nullptr;
-  int slot;
   float s;
   int mode;
   struct Frag { float x[N]; };
-  // logical slot 0 = the op's table row `slot` (descriptor loads, gs_kernels.hip: load_tv)
-  __device__ int phys(int k) const { return k == 0 ? slot : k; }
-  __device__ bool active() const { return true; }
   __device__ bool fast_ok(const TV& v) const { return v.vec(0); }
   template <bool F>
   __device__ void load(const TV& v, int64_t e0, uint32_t lo, Frag& f) const {
@@ -864,19 +823,12 @@ struct ScaleOp {
 // nt_read_once below).  G: chunks per group (the raw partials of a small plan take
 // 8: one group per workgroup, every access of the workgroup in flight at once)
 template <int N, int DT, bool NT = false, int G = GS_G_RED>
-struct SqnormOp {
-  static constexpr int kN = N;
+struct SqnormOp : SlotOpBase<N> {
   static constexpr int kG = G;
   static constexpr int kRed = 1;
   static constexpr int kRedGrid = 8192;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_SQNORM;
-  float* partials = nullptr;
-  int slot;
   struct Frag { float x[N]; };
-  // logical slot 0 = the op's table row `slot` (descriptor loads, gs_kernels.hip: load_tv)
-  __device__ int phys(int k) const { return k == 0 ? slot : k; }
-  __device__ bool active() const { return true; }
   __device__ bool fast_ok(const TV& v) const { return v.vec(0); }
   template <bool F>
   __device__ void load(const TV& v, int64_t e0, uint32_t lo, Frag& f) const {
@@ -891,18 +843,12 @@ struct SqnormOp {
 
 // Σ x (debug bucket checksums)
 template <int N, int DT>
-struct SumOp {
-  static constexpr int kN = N;
+struct SumOp : SlotOpBase<N> {
   static constexpr int kG = GS_G_RED;
   static constexpr int kRed = 1;
   static constexpr int kRedGrid = 8192;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_SUM;
-  float* partials = nullptr;
-  int slot;
   struct Frag { float x[N]; };
-  __device__ int phys(int k) const { return k == 0 ? slot : k; }
-  __device__ bool active() const { return true; }
   __device__ bool fast_ok(const TV& v) const { return v.vec(0); }
   template <bool F>
   __device__ void load(const TV& v, int64_t e0, uint32_t lo, Frag& f) const {
@@ -916,20 +862,13 @@ struct SumOp {
 };
 
 template <int N, int DT>
-struct UnscaleOp {
-  static constexpr int kN = N;
+struct UnscaleOp : SlotOpBase<N> {
   static constexpr int kG = GS_G_RED;
   static constexpr int kRed = 2;
   static constexpr int kRedGrid = 8192;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_UNSCALE;
-  float* partials = nullptr;
-  int slot;
   const float* inv;  // nullable
   struct Frag { float x[N]; };
-  // logical slot 0 = the op's table row `slot` (descriptor loads, gs_kernels.hip: load_tv)
-  __device__ int phys(int k) const { return k == 0 ? slot : k; }
-  __device__ bool active() const { return true; }
   __device__ bool fast_ok(const TV& v) const { return v.vec(0); }
   template <bool F>
   __device__ void load(const TV& v, int64_t e0, uint32_t lo, Frag& f) const {
@@ -959,19 +898,12 @@ struct UnscaleOp {
 // NT: non-temporal loads of the grads (above the cache size, nt_read_once: the Σg² pass
 // before it could not leave them in the cache either)
 template <int N, int DT, bool NT = false>
-struct ClipScaleOp {
-  static constexpr int kN = N;
+struct ClipScaleOp : SlotOpBase<N> {
   static constexpr int kG = GS_G_UNPACK;
-  static constexpr int kRed = 0;
-  static constexpr int kRedGrid = kGridLimit;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_SCALE;
-  float* partials = nullptr;
-  int slot;
   ClipArgs clip{};
   float gsv = 1.f;
   struct Frag { float x[N]; };
-  __device__ int phys(int k) const { return k == 0 ? slot : k; }
   __device__ bool active() const { return gsv != 1.f; }  // uniform; a NaN coefficient scales
   __device__ bool fast_ok(const TV& v) const { return v.vec(0); }
   template <bool F>
@@ -989,14 +921,9 @@ struct ClipScaleOp {
 // SGD: slots 0 = p (f32), 1 = g (GD), 2 = momentum buffer (f32), 3 = low-precision copy (LD)
 // NTG: non-temporal loads of the grad (the load policy above; p and the state stay cached)
 template <int N, int GD, int LD, bool NTG = true>
-struct SgdOp {
-  static constexpr int kN = N;
+struct SgdOp : OpBase<N> {
   static constexpr int kG = GS_G_SGD;
-  static constexpr int kRed = 0;
-  static constexpr int kRedGrid = kGridLimit;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_SGD;
-  float* partials = nullptr;
   SgdHyper h;
   const float* gscale;
   const float* found_inf;
@@ -1006,7 +933,6 @@ struct SgdOp {
   bool use_gs = false;           // the grad multiplier gsv applies (set by load_hyper)
   float gsv = 1.f;
   struct Frag { float p[N], g[N], b[N]; };
-  __device__ int phys(int k) const { return k; }
   __device__ bool active() const { return found_inf == nullptr || *found_inf == 0.f; }
   __device__ bool fast_ok(const TV& v) const {
     return v.vec(0) && v.vec(1) && (h.mom == 0.f || v.vec(2)) && (LD < 0 || v.vec(3));
@@ -1020,20 +946,7 @@ struct SgdOp {
   template <bool F>
   __device__ void apply(const TV& v, int64_t e0, uint32_t lo, Frag& f, float&) const {
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-      float g = f.g[i];
-      if (use_gs) g = g * gsv;                      // clip_grad_norm_ / unscale: grads *= coef
-      if (h.maximize) g = -g;
-      if (h.wd != 0.f) g = fmaf(h.wd, f.p[i], g);   // grad.add(param, alpha=wd)
-      float d = g;
-      if (h.mom != 0.f) {
-        // buf = clone(g) on the first step, else buf.mul_(mom).add_(g, alpha=1-damp)
-        const float b = h.first ? g : fmaf(h.omd, g, f.b[i] * h.mom);
-        f.b[i] = b;
-        d = h.nesterov ? fmaf(h.mom, b, g) : b;     // g.add(buf, alpha=mom)
-      }
-      f.p[i] = fmaf(-h.lr, d, f.p[i]);              // param.add_(d, alpha=-lr)
-    }
+    for (int i = 0; i < N; ++i) sgd_update(h, use_gs, gsv, f.g[i], &f.p[i], &f.b[i]);  // f.b: not read unloaded
     st<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.p);
     if (h.mom != 0.f) st<GS_F32, N, F>(v.ptr[2], e0, lo, v.numel, v.vec(2), f.b);
     if constexpr (LD >= 0) st<LD, N, F>(v.ptr[3], e0, lo, v.numel, v.vec(3), f.p);
@@ -1050,14 +963,9 @@ struct SgdOp {
 // (include/gsync.h) rounds every multiply and add once.
 // NTG: non-temporal loads of the grad (false right behind gs_lars_norms when it fits the cache)
 template <int N, int GD, int LD = -1, bool NTG = false>
-struct LarsOp {
-  static constexpr int kN = N;
+struct LarsOp : OpBase<N> {
   static constexpr int kG = GS_G_SGD;
-  static constexpr int kRed = 0;
-  static constexpr int kRedGrid = kGridLimit;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_LARS;
-  float* partials = nullptr;
   LarsHyper h;
   const float* norms;            // [2n]: Σp², Σg² per tensor
   const int32_t* adapt;          // [n]
@@ -1067,7 +975,6 @@ struct LarsOp {
   bool use_gs = false;           // the grad multiplier gsv applies (set by load_hyper)
   float gsv = 1.f;
   struct Frag { float p[N], g[N], b[N], slr, wd; };
-  __device__ int phys(int k) const { return k; }
   __device__ bool active() const { return found_inf == nullptr || *found_inf == 0.f; }
   __device__ bool fast_ok(const TV& v) const {
     return v.vec(0) && v.vec(1) && (h.mom == 0.f || v.vec(2)) && (LD < 0 || v.vec(3));
@@ -1083,18 +990,7 @@ struct LarsOp {
   template <bool F>
   __device__ void apply(const TV& v, int64_t e0, uint32_t lo, Frag& f, float&) const {
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-      float g = f.g[i];
-      if (use_gs) g = g * gsv;
-      if (f.wd != 0.f) g = g + f.wd * f.p[i];
-      float d = g;
-      if (h.mom != 0.f) {
-        const float b = f.b[i] * h.mom + g;
-        f.b[i] = b;
-        d = b;
-      }
-      f.p[i] = f.p[i] - f.slr * d;
-    }
+    for (int i = 0; i < N; ++i) lars_update(h, f.slr, f.wd, use_gs, gsv, f.g[i], &f.p[i], &f.b[i]);
     st<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.p);
     if (h.mom != 0.f) st<GS_F32, N, F>(v.ptr[2], e0, lo, v.numel, v.vec(2), f.b);
     if constexpr (LD >= 0) st<LD, N, F>(v.ptr[3], e0, lo, v.numel, v.vec(3), f.p);
@@ -1110,21 +1006,15 @@ struct LarsOp {
 #define GS_G_LAMB 4
 #endif
 template <int N, int LD = -1>
-struct LambOp {
-  static constexpr int kN = N;
+struct LambOp : OpBase<N> {
   static constexpr int kG = GS_G_LAMB;
-  static constexpr int kRed = 0;
-  static constexpr int kRedGrid = kGridLimit;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_LAMB;
-  float* partials = nullptr;
   LambHyper h;
   const float* norms;            // [2n]: Σp², Σu² per tensor
   const int32_t* adapt;          // [n]
   const float* found_inf;
   const float* hyper = nullptr;  // [lr, bc1, bc2s] in device memory (gs_plan_set_hyper_source)
   struct Frag { float p[N], m[N], v[N], slr, wd; };
-  __device__ int phys(int k) const { return k; }
   __device__ bool active() const { return found_inf == nullptr || *found_inf == 0.f; }
   __device__ bool fast_ok(const TV& tv) const {
     return tv.vec(0) && tv.vec(2) && tv.vec(3) && (LD < 0 || tv.vec(4));
@@ -1150,14 +1040,9 @@ struct LambOp {
 
 // Adam/AdamW: slots 0 = p, 1 = g, 2 = exp_avg, 3 = exp_avg_sq, 4 = low-precision copy
 template <int N, int GD, int LD, bool NTG = true>
-struct AdamOp {
-  static constexpr int kN = N;
+struct AdamOp : OpBase<N> {
   static constexpr int kG = GS_G_ADAM;
-  static constexpr int kRed = 0;
-  static constexpr int kRedGrid = kGridLimit;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_ADAM;
-  float* partials = nullptr;
   AdamHyper h;
   const float* gscale;
   const float* found_inf;
@@ -1167,7 +1052,6 @@ struct AdamOp {
   bool use_gs = false;           // the grad multiplier gsv applies (set by load_hyper)
   float gsv = 1.f;
   struct Frag { float p[N], g[N], m[N], v[N]; };
-  __device__ int phys(int k) const { return k; }
   __device__ bool active() const { return found_inf == nullptr || *found_inf == 0.f; }
   __device__ bool fast_ok(const TV& tv) const {
     return tv.vec(0) && tv.vec(1) && tv.vec(2) && tv.vec(3) && (LD < 0 || tv.vec(4));
@@ -1182,21 +1066,7 @@ struct AdamOp {
   template <bool F>
   __device__ void apply(const TV& tv, int64_t e0, uint32_t lo, Frag& f, float&) const {
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-      float g = f.g[i];
-      if (use_gs) g = g * gsv;
-      if (h.maximize) g = -g;
-      float p = f.p[i];
-      if (h.wd != 0.f) {
-        if (h.adamw) p = p * h.decay;                       // param.mul_(1 - lr*wd)
-        else g = fmaf(h.wd, p, g);                          // grad.add(param, alpha=wd)
-      }
-      const float m = fmaf(h.w1, g - f.m[i], f.m[i]);       // exp_avg.lerp_(g, 1-b1)  (w<0.5)
-      const float v = fmaf(h.w2 * g, g, f.v[i] * h.b2);     // mul_(b2).addcmul_(g, g, 1-b2)
-      const float denom = sqrtf(v) / h.bc2s + h.eps;        // sqrt(v)/bc2_sqrt + eps
-      p = fmaf(h.step_size, m / denom, p);                  // addcdiv_(m, denom, -lr/bc1)
-      f.p[i] = p; f.m[i] = m; f.v[i] = v;
-    }
+    for (int i = 0; i < N; ++i) adam_update(h, use_gs, gsv, f.g[i], &f.p[i], &f.m[i], &f.v[i]);
     st<GS_F32, N, F>(tv.ptr[0], e0, lo, tv.numel, tv.vec(0), f.p);
     st<GS_F32, N, F>(tv.ptr[2], e0, lo, tv.numel, tv.vec(2), f.m);
     st<GS_F32, N, F>(tv.ptr[3], e0, lo, tv.numel, tv.vec(3), f.v);
@@ -1216,22 +1086,15 @@ struct AdamOp {
 // NTS: non-temporal loads of the source (a read-once stream larger than the Infinity Cache,
 // nt_read_once); the average keeps cached loads, as every read-modify-write stream here.
 template <int N, int SD, int LD = -1, bool NTS = false>
-struct EmaOp {
-  static constexpr int kN = N;
+struct EmaOp : OpBase<N> {
   static constexpr int kG = GS_G_SGD;
-  static constexpr int kRed = 0;
-  static constexpr int kRedGrid = kGridLimit;
-  static constexpr int kRedFuseGrid = GS_RED_FUSE_GRID;
   static constexpr int kKind = GS_OP_EMA;
-  float* partials = nullptr;
   float w;
   int copy;
   const float* hyper = nullptr;  // [w, copy flag] in device memory (gs_plan_set_hyper_source)
   float wm1 = 0.f;               // w - 1 (set by load_hyper)
   bool high = false;             // |w| >= 0.5 (set by load_hyper)
   struct Frag { float a[N], s[N]; };
-  __device__ int phys(int k) const { return k; }
-  __device__ bool active() const { return true; }
   __device__ bool fast_ok(const TV& v) const { return v.vec(0) && v.vec(1) && (LD < 0 || v.vec(2)); }
   template <bool F>
   __device__ void load(const TV& v, int64_t e0, uint32_t lo, Frag& f) const {
@@ -1245,10 +1108,10 @@ struct EmaOp {
       for (int i = 0; i < N; ++i) f.a[i] = f.s[i];
     } else if (high) {
 #pragma unroll
-      for (int i = 0; i < N; ++i) f.a[i] = fmaf(wm1, f.s[i] - f.a[i], f.s[i]);
+      for (int i = 0; i < N; ++i) f.a[i] = ema_lerp(true, w, wm1, f.a[i], f.s[i]);
     } else {
 #pragma unroll
-      for (int i = 0; i < N; ++i) f.a[i] = fmaf(w, f.s[i] - f.a[i], f.a[i]);
+      for (int i = 0; i < N; ++i) f.a[i] = ema_lerp(false, w, wm1, f.a[i], f.s[i]);
     }
     st<GS_F32, N, F>(v.ptr[0], e0, lo, v.numel, v.vec(0), f.a);
     // the copy is the cast of the stored fp32 value (from_f32 pins it: no fma folded into the cast)
@@ -1261,16 +1124,15 @@ __device__ __forceinline__ void load_hyper(EmaOp<N, SD, LD, NTS>& op) {
     op.w = op.hyper[0];
     op.copy = op.hyper[1] != 0.f;
   }
-  op.wm1 = op.w - 1.0f;
-  op.high = fabsf(op.w) >= 0.5f;
+  ema_form(op.w, &op.wm1, &op.high);
 }
 
 // The update's grad multiplier, formed once per workgroup (uniform): *gscale
 // (AMP unscale / a precomputed clip coefficient) or, with a folded clip, the
 // clip coefficient itself — from a finished Σg² or from the Σg² kernel's group
 // sums (lane j reads group j and the wave folds them: the fused combine's own
-// last step, so the result is bit-identical to gs_sqnorm's), then exactly
-// clip_coef_kernel's arithmetic.  Workgroup 0 publishes [Σg², coef, norm].
+// last step, so the result is bit-identical to gs_sqnorm's), then clip_factor
+// (gs_math.h), whose quotient is clip_coef_kernel's.  Workgroup 0 publishes [Σg², coef, norm].
 __device__ __forceinline__ float clip_multiplier(const ClipArgs& c, const float* gscale) {
   // wave 0 forms the coefficient, the workgroup reads it from LDS: one wave per
   // workgroup reads the partial sums (every wave of every workgroup re-reading the
@@ -1298,14 +1160,8 @@ __device__ __forceinline__ float clip_multiplier(const ClipArgs& c, const float*
     } else {
       sq = c.sq[0];
     }
-    const float s = gscale ? *gscale : 1.f;
-    if (gscale) sq = sq * (s * s);                    // the norm of the unscaled grads
-    sq = sq * c.sq_mul;
-    const float nrm = sqrtf(sq);
-    float coef = c.max_norm / (nrm + c.eps);
-    coef = c.torch_clamp ? (coef >= 1.f ? 1.f : coef) : (coef < 1.f ? coef : 1.f);
-    if (gscale) coef = coef * s;
-    coef = coef * c.coef_mul;
+    float nrm;
+    const float coef = clip_factor(c, gscale, &sq, &nrm);
     if (threadIdx.x == 0) {
       s_coef = coef;
       if (c.out && blockIdx.x == 0) {
@@ -1364,8 +1220,7 @@ __global__ void clip_coef_kernel(const float* sq, float max_norm, float eps, flo
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     const float nrm = sqrtf(sq[0]);
     if (norm) norm[0] = nrm;
-    const float c = max_norm / (nrm + eps);
-    coef[0] = c < 1.f ? c : 1.f;
+    coef[0] = clip_coef(nrm, max_norm, eps, 0);
   }
 }
 
@@ -1405,7 +1260,7 @@ template <class Op>
 int launch(gs_plan* p, Op op, void* stream, float* red_out = nullptr, int accumulate = 0,
            int groups_only = 0) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (p->n == 0 || p->segs.empty()) {
+  if (p->elems == 0) {  // no tensor has an element: nothing to launch
     if (Op::kRed != 0 && red_out && !accumulate) HIP_RET(hipMemsetAsync(red_out, 0, 4, s));
     return GS_OK;
   }
@@ -1512,21 +1367,5 @@ int launch(gs_plan* p, Op op, void* stream, float* red_out = nullptr, int accumu
 bool flat_aligned(const void* flat) { return (reinterpret_cast<uintptr_t>(flat) & 15u) == 0; }
 
 }  // namespace
-
-#define GS_DISPATCH_FLOAT(DT, NAME, ...)                        \
-  switch (DT) {                                                 \
-    case GS_F32: { constexpr int NAME = GS_F32; __VA_ARGS__; break; }   \
-    case GS_BF16: { constexpr int NAME = GS_BF16; __VA_ARGS__; break; } \
-    case GS_F16: { constexpr int NAME = GS_F16; __VA_ARGS__; break; }   \
-    default: return fail(GS_EINVAL, "unsupported floating dtype");      \
-  }
-
-#define GS_DISPATCH_LOWP(DT, NAME, ...)                                  \
-  switch (DT) {                                                          \
-    case -1: { constexpr int NAME = -1; __VA_ARGS__; break; }            \
-    case GS_BF16: { constexpr int NAME = GS_BF16; __VA_ARGS__; break; }  \
-    case GS_F16: { constexpr int NAME = GS_F16; __VA_ARGS__; break; }    \
-    default: return fail(GS_EINVAL, "unsupported low-precision dtype");  \
-  }
 
 }  // namespace gs

@@ -1,11 +1,12 @@
 // Host implementation of the plan ops, used for CPU tensors (the CPU/gloo
-// configuration: BASELINE config 1).  Same arithmetic as gs_kernels.hip,
-// element for element (explicit fmaf, -ffp-contract=off), so a CPU run and a
-// GPU run of the engine agree bit for bit on the pack / unpack / optimizer
-// math.  A HIP plan never reaches this file.
+// configuration: BASELINE config 1).  The arithmetic is the device ops', element
+// for element: both sides compile the update, clip and conversion functions of
+// gs_math.h (-ffp-contract=off), so a CPU run and a GPU run of the engine agree
+// bit for bit on the pack / unpack / optimizer math.  A HIP plan never reaches
+// this file.
 //
 // Speed: loops are instantiated per dtype combination (no per-element type
-// switch) so the compiler vectorises them (built with -mavx2 -mfma: std::fmaf
+// switch) so the compiler vectorises them (built with -mavx2 -mfma: fmaf
 // is one vfmadd, bit-identical to the software fmaf), and large plans are
 // split over gs_set_host_threads() threads (torch's intra-op thread count).
 // Elementwise results do not depend on the split; the Σg² reductions stay
@@ -20,48 +21,15 @@
 namespace gs {
 namespace {
 
-inline float bf16_to_f32(uint16_t h) {
-  uint32_t u = static_cast<uint32_t>(h) << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-inline uint16_t f32_to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7FC0;
-  return static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-inline float f16_to_f32(uint16_t h) {
-  _Float16 x;
-  std::memcpy(&x, &h, 2);
-  return static_cast<float>(x);
-}
-inline uint16_t f32_to_f16(float f) {
-  _Float16 x = static_cast<_Float16>(f);
-  uint16_t h;
-  std::memcpy(&h, &x, 2);
-  return h;
-}
-
-
 template <int DT>
 inline float ldT(const void* base, int64_t i) {
   if constexpr (DT == GS_F32) return static_cast<const float*>(base)[i];
-  else if constexpr (DT == GS_BF16) return bf16_to_f32(static_cast<const uint16_t*>(base)[i]);
-  else return f16_to_f32(static_cast<const uint16_t*>(base)[i]);
+  else return to_f32<DT>(static_cast<const uint16_t*>(base)[i]);
 }
 template <int DT>
 inline void stT(void* base, int64_t i, float v) {
   if constexpr (DT == GS_F32) static_cast<float*>(base)[i] = v;
-  else if constexpr (DT == GS_BF16) static_cast<uint16_t*>(base)[i] = f32_to_bf16(v);
-  else static_cast<uint16_t*>(base)[i] = f32_to_f16(v);
-}
-template <int DT>
-inline float roundT(float v) {
-  if constexpr (DT == GS_F32) return v;
-  else if constexpr (DT == GS_BF16) return bf16_to_f32(f32_to_bf16(v));
-  else return f16_to_f32(f32_to_f16(v));
+  else static_cast<uint16_t*>(base)[i] = from_f32<DT>(v);
 }
 inline void* slot(gs_plan* p, int s, int t) { return p->h_ptrs[static_cast<size_t>(s) * p->n + t]; }
 
@@ -99,25 +67,10 @@ void for_ranges(const gs_plan* p, F&& fn) {
   for (auto& th : pool) th.join();
 }
 
-#define GS_HOST_FLOAT(DT, NAME, ...)                                    \
-  switch (DT) {                                                         \
-    case GS_F32: { constexpr int NAME = GS_F32; __VA_ARGS__; break; }   \
-    case GS_BF16: { constexpr int NAME = GS_BF16; __VA_ARGS__; break; } \
-    case GS_F16: { constexpr int NAME = GS_F16; __VA_ARGS__; break; }   \
-    default: return fail(GS_EINVAL, "unsupported floating dtype");      \
-  }
-#define GS_HOST_LOWP(DT, NAME, ...)                                      \
-  switch (DT) {                                                          \
-    case -1: { constexpr int NAME = -1; __VA_ARGS__; break; }            \
-    case GS_BF16: { constexpr int NAME = GS_BF16; __VA_ARGS__; break; }  \
-    case GS_F16: { constexpr int NAME = GS_F16; __VA_ARGS__; break; }    \
-    default: return fail(GS_EINVAL, "unsupported low-precision dtype");  \
-  }
-
 }  // namespace
 
 int host_pack(gs_plan* p, int src_slot, int src_dt, void* flat, int flat_dt, float s, int mode) {
-  GS_HOST_FLOAT(src_dt, SD, GS_HOST_FLOAT(flat_dt, FD, {
+  GS_DISPATCH_FLOAT(src_dt, SD, GS_DISPATCH_FLOAT(flat_dt, FD, {
     const int fsz = dtype_size(FD);
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       const void* src = slot(p, src_slot, t);
@@ -128,7 +81,7 @@ int host_pack(gs_plan* p, int src_slot, int src_dt, void* flat, int flat_dt, flo
       } else if (mode == GS_SCALE_MUL) {
         for (int64_t i = i0; i < i1; ++i) stT<FD>(dst, i, ldT<SD>(src, i) * s);
       } else if (mode == GS_SCALE_DIV) {
-        for (int64_t i = i0; i < i1; ++i) stT<FD>(dst, i, roundT<FD>(ldT<SD>(src, i)) / s);
+        for (int64_t i = i0; i < i1; ++i) stT<FD>(dst, i, round_to<FD>(ldT<SD>(src, i)) / s);
       } else {
         for (int64_t i = i0; i < i1; ++i) stT<FD>(dst, i, ldT<SD>(src, i));
       }
@@ -139,7 +92,7 @@ int host_pack(gs_plan* p, int src_slot, int src_dt, void* flat, int flat_dt, flo
 
 int host_unpack(gs_plan* p, const void* flat, int flat_dt, int dst_slot, int dst_dt, float* sq,
                 int acc) {
-  GS_HOST_FLOAT(flat_dt, FD, GS_HOST_FLOAT(dst_dt, DD, {
+  GS_DISPATCH_FLOAT(flat_dt, FD, GS_DISPATCH_FLOAT(dst_dt, DD, {
     const int fsz = dtype_size(FD);
     if (sq) {  // serial: the double-precision Σ order is the oracle's
       double total = 0.0;
@@ -150,7 +103,7 @@ int host_unpack(gs_plan* p, const void* flat, int flat_dt, int dst_slot, int dst
         for (int64_t i = 0; i < p->numel[t]; ++i) {
           const float v = ldT<FD>(src, i);
           stT<DD>(dst, i, v);
-          const float r = roundT<DD>(v);
+          const float r = round_to<DD>(v);
           total += static_cast<double>(r) * r;
         }
       }
@@ -169,7 +122,7 @@ int host_unpack(gs_plan* p, const void* flat, int flat_dt, int dst_slot, int dst
 
 int host_unpack_check(gs_plan* p, const void* flat, int flat_dt, int dst_slot, int dst_dt, float* found) {
   std::atomic<int> bad{found[0] != 0.f ? 1 : 0};
-  GS_HOST_FLOAT(flat_dt, FD, GS_HOST_FLOAT(dst_dt, DD, {
+  GS_DISPATCH_FLOAT(flat_dt, FD, GS_DISPATCH_FLOAT(dst_dt, DD, {
     const int fsz = dtype_size(FD);
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       const void* src = static_cast<const char*>(flat) + p->off[t] * fsz;
@@ -179,7 +132,7 @@ int host_unpack_check(gs_plan* p, const void* flat, int flat_dt, int dst_slot, i
       for (int64_t i = i0; i < i1; ++i) {
         const float v = ldT<FD>(src, i);
         stT<DD>(dst, i, v);
-        b |= !std::isfinite(roundT<DD>(v));
+        b |= !std::isfinite(round_to<DD>(v));
       }
       if (b) bad.store(1);
     });
@@ -189,7 +142,7 @@ int host_unpack_check(gs_plan* p, const void* flat, int flat_dt, int dst_slot, i
 }
 
 int host_scale(gs_plan* p, int s_, int dt, float s, int mode) {
-  GS_HOST_FLOAT(dt, DT, {
+  GS_DISPATCH_FLOAT(dt, DT, {
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       void* x = slot(p, s_, t);
       if (mode == GS_SCALE_DIV)
@@ -208,7 +161,7 @@ int host_clip_scale(gs_plan* p, int s_, int dt, const ClipArgs& clip) {
 }
 
 int host_sqnorm(gs_plan* p, int s_, int dt, float* sq, int acc) {
-  GS_HOST_FLOAT(dt, DT, {
+  GS_DISPATCH_FLOAT(dt, DT, {
     double total = 0.0;
     for (int t = 0; t < p->n; ++t) {
       const void* x = slot(p, s_, t);
@@ -223,7 +176,7 @@ int host_sqnorm(gs_plan* p, int s_, int dt, float* sq, int acc) {
 }
 
 int host_sum(gs_plan* p, int s_, int dt, float* out, int acc) {
-  GS_HOST_FLOAT(dt, DT, {
+  GS_DISPATCH_FLOAT(dt, DT, {
     double total = 0.0;
     for (int t = 0; t < p->n; ++t) {
       const void* x = slot(p, s_, t);
@@ -235,10 +188,9 @@ int host_sum(gs_plan* p, int s_, int dt, float* out, int acc) {
 }
 
 int host_clip_coef(const float* sq, float max_norm, float eps, float* coef, float* norm) {
-  const float nrm = std::sqrt(sq[0]);
+  const float nrm = sqrtf(sq[0]);
   if (norm) norm[0] = nrm;
-  const float c = max_norm / (nrm + eps);
-  coef[0] = c < 1.f ? c : 1.f;
+  coef[0] = clip_coef(nrm, max_norm, eps, 0);
   return GS_OK;
 }
 
@@ -246,7 +198,7 @@ int host_unscale_check(gs_plan* p, int s_, int dt, const float* inv, float* foun
   std::atomic<int> bad{found[0] != 0.f ? 1 : 0};
   const bool scale = inv && inv[0] != 1.f;
   const float sc = scale ? inv[0] : 1.f;
-  GS_HOST_FLOAT(dt, DT, {
+  GS_DISPATCH_FLOAT(dt, DT, {
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       void* x = slot(p, s_, t);
       int b = 0;
@@ -290,14 +242,8 @@ float host_wave_sum(const float* x, int n, int stride) {
 
 float host_clip_factor(const ClipArgs& c, const float* gsc) {
   float sq = c.groups > 0 ? host_wave_sum(c.sq, c.groups, c.stride) : c.sq[0];
-  const float s = gsc ? gsc[0] : 1.f;
-  if (gsc) sq = sq * (s * s);
-  sq = sq * c.sq_mul;
-  const float nrm = std::sqrt(sq);
-  float coef = c.max_norm / (nrm + c.eps);
-  coef = c.torch_clamp ? (coef >= 1.f ? 1.f : coef) : (coef < 1.f ? coef : 1.f);
-  if (gsc) coef = coef * s;
-  coef = coef * c.coef_mul;
+  float nrm;
+  const float coef = clip_factor(c, gsc, &sq, &nrm);
   if (c.out) {
     c.out[0] = sq;
     c.out[1] = coef;
@@ -315,25 +261,22 @@ int host_sgd(gs_plan* p, int gdt, int ldt, const SgdHyper& h, const float* gsc, 
   }
   const bool has_gs = gsc != nullptr || clip != nullptr;
   const float gs = clip ? cf : (gsc ? gsc[0] : 1.f);
-  GS_HOST_FLOAT(gdt, GD, GS_HOST_LOWP(ldt, LD, {
+  GS_DISPATCH_FLOAT(gdt, GD, GS_DISPATCH_LOWP(ldt, LD, {
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       float* pp = static_cast<float*>(slot(p, 0, t));
       const void* gp = slot(p, 1, t);
       float* bp = static_cast<float*>(slot(p, 2, t));
       void* lp = slot(p, 3, t);
+      // a local copy: no store of the loop can alias it, so its branches are loop-invariant
+      const SgdHyper hh = h;
+      const bool has_b = hh.mom != 0.f, rd_b = has_b && !hh.first;  // bp is NULL without a momentum
       for (int64_t i = i0; i < i1; ++i) {
-        float g = ldT<GD>(gp, i);
-        if (has_gs) g = g * gs;
-        if (h.maximize) g = -g;
-        if (h.wd != 0.f) g = std::fmaf(h.wd, pp[i], g);
-        float d = g;
-        if (h.mom != 0.f) {
-          const float b = h.first ? g : std::fmaf(h.omd, g, bp[i] * h.mom);
-          bp[i] = b;
-          d = h.nesterov ? std::fmaf(h.mom, b, g) : b;
-        }
-        pp[i] = std::fmaf(-h.lr, d, pp[i]);
-        if constexpr (LD >= 0) stT<LD>(lp, i, pp[i]);
+        float x = pp[i], b = 0.f;
+        if (rd_b) b = bp[i];
+        sgd_update(hh, has_gs, gs, ldT<GD>(gp, i), &x, &b);
+        pp[i] = x;
+        if (has_b) bp[i] = b;
+        if constexpr (LD >= 0) stT<LD>(lp, i, x);
       }
     });
   }));
@@ -349,7 +292,7 @@ int host_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gsc
   }
   const bool has_gs = gsc != nullptr || clip != nullptr;
   const float gs = clip ? cf : (gsc ? gsc[0] : 1.f);
-  GS_HOST_FLOAT(gdt, GD, GS_HOST_LOWP(ldt, LD, {
+  GS_DISPATCH_FLOAT(gdt, GD, GS_DISPATCH_LOWP(ldt, LD, {
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       float* pp = static_cast<float*>(slot(p, 0, t));
       const void* gp = slot(p, 1, t);
@@ -357,18 +300,8 @@ int host_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gsc
       float* vp = static_cast<float*>(slot(p, 3, t));
       void* lp = slot(p, 4, t);
       for (int64_t i = i0; i < i1; ++i) {
-        float g = ldT<GD>(gp, i);
-        if (has_gs) g = g * gs;
-        if (h.maximize) g = -g;
-        float x = pp[i];
-        if (h.wd != 0.f) {
-          if (h.adamw) x = x * h.decay;
-          else g = std::fmaf(h.wd, x, g);
-        }
-        const float m = std::fmaf(h.w1, g - mp[i], mp[i]);
-        const float v = std::fmaf(h.w2 * g, g, vp[i] * h.b2);
-        const float denom = std::sqrt(v) / h.bc2s + h.eps;
-        x = std::fmaf(h.step_size, m / denom, x);
+        float x = pp[i], m = mp[i], v = vp[i];
+        adam_update(h, has_gs, gs, ldT<GD>(gp, i), &x, &m, &v);
         pp[i] = x;
         mp[i] = m;
         vp[i] = v;
@@ -379,13 +312,14 @@ int host_adam(gs_plan* p, int gdt, int ldt, const AdamHyper& h, const float* gsc
   return GS_OK;
 }
 
-// EMA / SWA averaging on the host (include/gsync.h, gs_ema_step): EmaOp's arithmetic with
-// the hardware fmaf.  Copy mode with an fp32 source is a memcpy: no float register sees the
+// EMA / SWA averaging on the host (include/gsync.h, gs_ema_step): EmaOp's arithmetic
+// (ema_form / ema_lerp).  Copy mode with an fp32 source is a memcpy: no float register sees the
 // words, so integer buffers and NaN patterns pass unchanged.
 int host_ema(gs_plan* p, int sdt, int ldt, float w, int copy) {
-  const float wm1 = w - 1.0f;
-  const bool high = std::fabs(w) >= 0.5f;
-  GS_HOST_FLOAT(sdt, SD, GS_HOST_LOWP(ldt, LD, {
+  float wm1;
+  bool high;
+  ema_form(w, &wm1, &high);
+  GS_DISPATCH_FLOAT(sdt, SD, GS_DISPATCH_LOWP(ldt, LD, {
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       float* ap = static_cast<float*>(slot(p, 0, t));
       const void* sp = slot(p, 1, t);
@@ -397,15 +331,9 @@ int host_ema(gs_plan* p, int sdt, int ldt, float w, int copy) {
           for (int64_t i = i0; i < i1; ++i) ap[i] = ldT<SD>(sp, i);
         }
       } else if (high) {
-        for (int64_t i = i0; i < i1; ++i) {
-          const float s = ldT<SD>(sp, i);
-          ap[i] = std::fmaf(wm1, s - ap[i], s);
-        }
+        for (int64_t i = i0; i < i1; ++i) ap[i] = ema_lerp(true, w, wm1, ap[i], ldT<SD>(sp, i));
       } else {
-        for (int64_t i = i0; i < i1; ++i) {
-          const float s = ldT<SD>(sp, i);
-          ap[i] = std::fmaf(w, s - ap[i], ap[i]);
-        }
+        for (int64_t i = i0; i < i1; ++i) ap[i] = ema_lerp(false, w, wm1, ap[i], ldT<SD>(sp, i));
       }
       if constexpr (LD >= 0)
         for (int64_t i = i0; i < i1; ++i) stT<LD>(lp, i, ap[i]);
@@ -444,7 +372,7 @@ static void blockwise_sq_sums(const gs_plan* p, float* norms, Tensor&& tensor) {
 }
 
 int host_lars_norms(gs_plan* p, int gdt, float* norms) {
-  GS_HOST_FLOAT(gdt, GD, {
+  GS_DISPATCH_FLOAT(gdt, GD, {
     blockwise_sq_sums(p, norms, [&](int t) {
       const float* pp = static_cast<const float*>(slot(p, 0, t));
       const void* gp = slot(p, 1, t);
@@ -463,7 +391,7 @@ int host_lars(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* nor
   std::vector<float> slr(p->n), wdt(p->n);
   for (int t = 0; t < p->n; ++t)
     lars_coef(h, norms[2 * t], norms[2 * t + 1], p->adapt.empty() ? 1 : p->adapt[t], has_m, m, &slr[t], &wdt[t]);
-  GS_HOST_FLOAT(gdt, GD, GS_HOST_LOWP(ldt, LD, {
+  GS_DISPATCH_FLOAT(gdt, GD, GS_DISPATCH_LOWP(ldt, LD, {
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       float* pp = static_cast<float*>(slot(p, 0, t));
       const void* gp = slot(p, 1, t);
@@ -471,17 +399,12 @@ int host_lars(gs_plan* p, int gdt, int ldt, const LarsHyper& h, const float* nor
       [[maybe_unused]] void* lp = slot(p, 3, t);
       const float lr_t = slr[t], wd_t = wdt[t];
       for (int64_t i = i0; i < i1; ++i) {
-        float g = ldT<GD>(gp, i);
-        if (has_m) g = g * m;
-        if (wd_t != 0.f) g = g + wd_t * pp[i];
-        float d = g;
-        if (h.mom != 0.f) {
-          const float b = bp[i] * h.mom + g;
-          bp[i] = b;
-          d = b;
-        }
-        pp[i] = pp[i] - lr_t * d;
-        if constexpr (LD >= 0) stT<LD>(lp, i, pp[i]);
+        float x = pp[i], b = 0.f;
+        if (h.mom != 0.f) b = bp[i];  // bp may be NULL without a momentum
+        lars_update(h, lr_t, wd_t, has_m, m, ldT<GD>(gp, i), &x, &b);
+        pp[i] = x;
+        if (h.mom != 0.f) bp[i] = b;
+        if constexpr (LD >= 0) stT<LD>(lp, i, x);
       }
     });
   }));
@@ -497,7 +420,7 @@ int host_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, con
   if (fi && fi[0] != 0.f) return GS_OK;
   const bool has_m = gsc != nullptr;
   const float mul = gsc ? gsc[0] : 1.f;
-  GS_HOST_FLOAT(gdt, GD, {
+  GS_DISPATCH_FLOAT(gdt, GD, {
     blockwise_sq_sums(p, norms, [&](int t) {
       const float* pp = static_cast<const float*>(slot(p, 0, t));
       const void* gp = slot(p, 1, t);
@@ -524,7 +447,7 @@ int host_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const
     slr[t] = lamb_coef(h, norms[2 * t], norms[2 * t + 1], ad);
     wdt[t] = ad != 0 ? h.wd : 0.f;
   }
-  GS_HOST_LOWP(ldt, LD, {
+  GS_DISPATCH_LOWP(ldt, LD, {
     for_ranges(p, [&](int t, int64_t i0, int64_t i1) {
       float* pp = static_cast<float*>(slot(p, 0, t));
       const float* mp = static_cast<const float*>(slot(p, 2, t));
@@ -595,7 +518,7 @@ void host_eval_rows(const void* logits, const int64_t* labels, int64_t B, int K,
 int host_eval_accumulate(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
                          int64_t n_valid, const EvalTopk& topk, int64_t ignore_index, void* ws, void* acc) {
   EvalRow* wp = static_cast<EvalRow*>(ws);
-  GS_HOST_FLOAT(dt, DT, host_eval_rows<DT>(logits, labels, B, K, row_stride, n_valid, ignore_index, wp));
+  GS_DISPATCH_FLOAT(dt, DT, host_eval_rows<DT>(logits, labels, B, K, row_stride, n_valid, ignore_index, wp));
   int64_t* ap = static_cast<int64_t*>(acc);
   double total = 0.0;
   for (int64_t r = 0; r < B; ++r) {  // ascending row order

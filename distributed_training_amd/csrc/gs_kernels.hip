@@ -36,21 +36,15 @@ static size_t table_bytes(const gs_plan* p) {
 
 int hip_plan_upload_static(gs_plan* p) {
   DeviceGuard g(p->device);
-  const size_t sz_segs = sizeof(Seg) * p->segs.size();
-  const size_t sz_tb = sizeof(int32_t) * p->task_begin.size();
   const size_t sz_n = sizeof(int64_t) * p->n;
   const size_t sz_ch = sizeof(ChunkDesc) * p->chunks.size();
   auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  // segs | task_begin | numel | off | chunks | voff (layout of gs_plan::args)
-  const size_t total = al(sz_segs) + al(sz_tb) + al(sz_n) * 3 + al(sz_ch);
+  // numel | off | chunks | voff (layout of gs_plan::args); never empty: hipMalloc(0) gives NULL
+  const size_t total = std::max<size_t>(256, al(sz_n) * 3 + al(sz_ch));
   HIP_RET(hipMalloc(&p->d_static, total));
   char* base = static_cast<char*>(p->d_static);
   std::vector<char> h(total, 0);
   size_t o = 0;
-  if (sz_segs) std::memcpy(h.data() + o, p->segs.data(), sz_segs);
-  o += al(sz_segs);
-  std::memcpy(h.data() + o, p->task_begin.data(), sz_tb);
-  o += al(sz_tb);
   if (sz_n) std::memcpy(h.data() + o, p->numel.data(), sz_n);
   o += al(sz_n);
   if (sz_n) std::memcpy(h.data() + o, p->off.data(), sz_n);
@@ -366,7 +360,7 @@ int hip_sqnorm_partial(gs_plan* p, int slot, int dt, float* groups_out, int32_t*
   // caller memory on a small plan (<= 4 Ki chunks: a ZeRO shard at N = 8): one partial per
   // workgroup of a balanced grid, no counters and no combine — the kernel ends with its
   // last store (groups of 8 chunks, one per workgroup, measured 0.7 µs slower: r5f)
-  if (!own && !p->chunks.empty() && p->n > 0 && !p->segs.empty() &&
+  if (!own && p->elems > 0 &&
       static_cast<int64_t>(p->chunks.size()) <= kRawChunksMax) {
     GS_TRY_RET(sqnorm_launch(p, slot, dt, groups_out, 0, 2, stream));
     if (n_groups) *n_groups = p->red_groups;
@@ -378,7 +372,7 @@ int hip_sqnorm_partial(gs_plan* p, int slot, int dt, float* groups_out, int32_t*
     return GS_OK;
   }
   const int cap = std::min(p->grid_cap, red_grid_cap(SqnormOp<kUnit, GS_F32>::kRedGrid));
-  const bool groups = !p->chunks.empty() && p->n > 0 && !p->segs.empty() &&
+  const bool groups = p->elems > 0 &&
                       red_fuse_groups() > 0 && cap <= kRedFuseMaxGrid;
   if (groups) {
     GS_TRY_RET(sqnorm_launch(p, slot, dt, groups_out, 0, 1, stream));

@@ -38,10 +38,6 @@ gs::PlanArgs gs_plan::args() const {
   auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   char* base = static_cast<char*>(d_static);
   size_t o = 0;
-  a.segs = reinterpret_cast<const Seg*>(base + o);
-  o += al(sizeof(Seg) * segs.size());
-  a.task_begin = reinterpret_cast<const int32_t*>(base + o);
-  o += al(sizeof(int32_t) * task_begin.size());
   a.numel = reinterpret_cast<const int64_t*>(base + o);
   o += al(sizeof(int64_t) * n);
   a.off = reinterpret_cast<const int64_t*>(base + o);
@@ -60,7 +56,6 @@ gs::PlanArgs gs_plan::args() const {
   a.align = reinterpret_cast<const uint32_t*>(static_cast<char*>(d_table) +
                                               sizeof(void*) * GS_PLAN_SLOTS * n);
   a.n = n;
-  a.n_tasks = static_cast<int32_t>(task_begin.size()) - 1;
   a.n_chunks = static_cast<int32_t>(chunks.size());
   return a;
 }
@@ -98,23 +93,52 @@ static void build_chunk_map(gs_plan* p) {
   }
 }
 
-// Task size (units) of a plan.  Every task is one workgroup's work; 256 CUs
-// hold 2048 resident workgroups (256 CUs x 8).  Plans up to
-// ~1920 x 16 Ki elements are cut into ~kTargetTasks tasks: one wave of
-// workgroups evenly spread over the CUs (no second partial round), rounded to
-// whole 256-lane iterations.  Larger plans keep 16 Ki-element tasks
-// (kSegUnits): the interleaved sweep (profiles/r1d_sweep_tasks_nt.jsonl)
-// puts 64 Ki-element tasks 20-25 % below 8-16 Ki-element ones on pack/unpack
-// of 120 M-element plans, while a second round of tasks costs little there.
-// Optimizer-update plans ask for 512-unit tasks instead (gs_plan_create_ex,
-// multi_tensor.UPDATE_TASK_UNITS): five streams per element make the
-// per-task descriptor prologue cheap relative to the data, and a short task
-// per workgroup streams +2-8 % faster (profiles/r1r_grid_sweep.jsonl).
-int64_t plan_task_units(int64_t total_units) {
+// The plan's task decomposition: public metadata (gs_plan_task_units / gs_plan_n_tasks),
+// reported and not acted on.  It is the work split of the first engine, whose
+// workgroups took one task each; the chunk-map kernels walk chunks / voff only, so the
+// rules below are kept for what they return and no table is built from them.
+constexpr int kSegUnits = 4096;     // largest default task: 16 Ki elements
+constexpr int kMinTaskUnits = 256;  // one unit per lane of a 256-thread workgroup
+constexpr int kTargetTasks = 1920;  // < 2048 resident workgroups (256 CUs x 8)
+constexpr int kMaxTensorsPerTask = 64;  // tensors sharing one task
+
+// Default task size (units): plans up to ~1920 x 16 Ki elements are cut into
+// ~kTargetTasks tasks, rounded to whole 256-lane iterations; larger plans keep
+// kSegUnits.  gs_plan_create_ex's task_units overrides it (optimizer-update plans ask
+// for 512, multi_tensor.UPDATE_TASK_UNITS).  What the first engine measured for these
+// sizes is history: profiles/r1d_sweep_tasks_nt.jsonl, profiles/r1r_grid_sweep.jsonl.
+static int64_t plan_task_units(int64_t total_units) {
   const int64_t target = kTargetTasks;
   int64_t u = (total_units + target - 1) / target;
   u = (u + kBlock - 1) / kBlock * kBlock;
   return std::max<int64_t>(kMinTaskUnits, std::min<int64_t>(kSegUnits, u));
+}
+
+// Tasks of a plan with `task_units` (even) units per task.  A tensor counts in even
+// units.  One larger than a task is shared by ceil(units / task_units) tasks of its own
+// (the first engine's interleaved parts); smaller tensors share a task, in order, while
+// they fit and up to kMaxTensorsPerTask of them.
+static int64_t plan_count_tasks(const gs_plan* p, int64_t task_units) {
+  int64_t n_tasks = 0, tu = 0;
+  int tc = 0;  // tensors in the open task (0: none open)
+  for (int t = 0; t < p->n; ++t) {
+    int64_t units = (p->numel[t] + kUnit - 1) / kUnit;
+    if (units == 0) continue;
+    units += units & 1;
+    if (units > task_units) {
+      n_tasks += (units + task_units - 1) / task_units;
+      tc = 0;
+      continue;
+    }
+    if (tc == 0 || tu + units > task_units || tc == kMaxTensorsPerTask) {
+      ++n_tasks;
+      tu = 0;
+      tc = 0;
+    }
+    tu += units;
+    ++tc;
+  }
+  return n_tasks;
 }
 
 extern "C" {
@@ -163,65 +187,16 @@ int gs_plan_create_ex(int device_kind, int device, int n_tensors, const int64_t*
     p->elems += numels[t];
   }
   p->flat_numel = rup(cur);
-  // segments and tasks
+  // the task decomposition: counted for gs_plan_task_units / gs_plan_n_tasks, not stored
   int64_t total_units = 0;
   for (int t = 0; t < n_tensors; ++t) total_units += (numels[t] + kUnit - 1) / kUnit;
   int64_t task_units =
       task_units_req > 0 ? std::max<int64_t>(kUnit, task_units_req) : plan_task_units(total_units);
-  task_units += task_units & 1;  // even (see the segment padding below)
+  task_units += task_units & 1;  // even, as the tensors' unit counts (plan_count_tasks)
   p->task_units = task_units;
-  for (int t = 0; t < n_tensors; ++t) {
-    int64_t units = (numels[t] + kUnit - 1) / kUnit;
-    if (units == 0) continue;
-    // even unit counts: an 8-element lane-step (two units) never straddles
-    // segments; the padding unit lies past the tensor's end and is masked
-    units += units & 1;
-    if (units > task_units) {
-      // a tensor larger than a task is shared by M single-segment tasks in
-      // interleaved chunks (part i takes lane-step chunks i, i+M, i+2M, ...):
-      // the M workgroups sweep the tensor front to back together instead of M
-      // far-apart streams (DRAM / Infinity-Cache locality; a torch-copy-like
-      // access pattern) — Seg.pad = M, unit_begin = i, units = the tensor's
-      const int64_t parts = (units + task_units - 1) / task_units;
-      for (int64_t i = 0; i < parts; ++i) {
-        Seg s{};
-        s.unit_begin = i;
-        s.tensor = t;
-        s.units = static_cast<int32_t>(units);
-        s.pad = static_cast<int32_t>(parts);
-        p->segs.push_back(s);
-      }
-      continue;
-    }
-    for (int64_t u = 0; u < units; u += task_units) {
-      Seg s{};
-      s.unit_begin = u;
-      s.tensor = t;
-      s.units = static_cast<int32_t>(std::min<int64_t>(task_units, units - u));
-      p->segs.push_back(s);
-    }
-  }
-  p->task_begin.push_back(0);
-  int64_t tu = 0;
-  int32_t tc = 0;
-  for (size_t i = 0; i < p->segs.size(); ++i) {
-    Seg& s = p->segs[i];
-    const bool alone = s.pad > 0;  // interleaved parts always own a task
-    if (tc > 0 && (alone || tu + s.units > task_units || tc == kMaxSegPerTask)) {
-      p->task_begin.push_back(static_cast<int32_t>(i));
-      tu = 0;
-      tc = 0;
-    }
-    s.task_off = static_cast<int32_t>(tu);
-    tu += alone ? task_units : s.units;  // a part fills its task
-    ++tc;
-  }
-  if (!p->segs.empty()) p->task_begin.push_back(static_cast<int32_t>(p->segs.size()));
-  const int n_tasks = static_cast<int>(p->task_begin.size()) - 1;
-  const int grid_cap = kMaxGrid;
-  p->grid = std::max(1, std::min(n_tasks, grid_cap));
+  p->n_tasks = static_cast<int>(plan_count_tasks(p, task_units));
   build_chunk_map(p);
-  p->grid_cap = grid_cap;
+  p->grid_cap = kMaxGrid;
   p->h_ptrs.assign(static_cast<size_t>(GS_PLAN_SLOTS) * n_tensors, nullptr);
   p->h_align.assign(n_tensors, 0u);
   if (device_kind == GS_DEV_HIP) {
@@ -254,7 +229,7 @@ int gs_plan_offsets(gs_plan* p, int64_t* out) {
   return GS_OK;
 }
 
-int gs_plan_n_tasks(gs_plan* p) { return p ? static_cast<int>(p->task_begin.size()) - 1 : -1; }
+int gs_plan_n_tasks(gs_plan* p) { return p ? p->n_tasks : -1; }
 
 int64_t gs_plan_task_units(gs_plan* p) { return p ? p->task_units : -1; }
 

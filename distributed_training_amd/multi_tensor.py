@@ -17,10 +17,11 @@ import torch
 
 from . import _lib as L
 
-# Task size (units of 4 elements) of an optimizer-update plan's segment table on
-# the GPU (gs_plan_create_ex task_units).  The device kernels stream through the
-# chunk map (gs_engine.h) whatever the task size; the segment table stays the
-# plan's public work decomposition (gs_plan_n_tasks / gs_plan_task_units).
+# Task size (units of 4 elements) asked for an optimizer-update plan on the GPU
+# (gs_plan_create_ex task_units).  The value is reported, not acted on: the device
+# kernels stream through the chunk map (gs_engine.h) whatever the task size, and the
+# plan only counts its public work decomposition from it (gs_plan_n_tasks /
+# gs_plan_task_units).
 UPDATE_TASK_UNITS = 512
 
 

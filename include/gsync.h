@@ -164,8 +164,8 @@ int gs_broadcast(gs_comm* c, const void* send, void* recv, int64_t count, int dt
  * buffer (per-tensor offsets aligned to `align_elems`, 0 = packed back to
  * back like torch's _flatten_dense_tensors / Reducer bucket), plus up to
  * GS_PLAN_SLOTS per-tensor pointer tables (param / grad / state...).
- * The work decomposition (segments + tasks) is built once on the host and
- * uploaded once; pointer tables are re-uploaded only when they change.
+ * The chunk map the kernels walk is built once on the host and uploaded
+ * once; pointer tables are re-uploaded only when they change.
  * replaces: T:include/ATen/native/cuda/MultiTensorApply.cuh:14-21 launch
  *           geometry (kILP 4, 64Ki-element chunks, <=110 tensors/launch)
  * ==================================================================== */
@@ -173,8 +173,9 @@ int gs_broadcast(gs_comm* c, const void* send, void* recv, int64_t count, int dt
 int gs_plan_create(int device_kind, int device, int n_tensors, const int64_t* numels,
                    int64_t align_elems, gs_plan** out);
 /* as gs_plan_create, with the work decomposition's task size pinned
- * (task_units units of 4 elements per workgroup task; 0 = automatic:
- * ~1920 tasks, one resident wave of workgroups) */
+ * (task_units units of 4 elements per task; 0 = automatic: ~1920 tasks).
+ * The value is reported (gs_plan_task_units, gs_plan_n_tasks), not acted
+ * on: the kernels walk the chunk map whatever the task size. */
 int gs_plan_create_ex(int device_kind, int device, int n_tensors, const int64_t* numels,
                       int64_t align_elems, int64_t task_units, gs_plan** out);
 /* Stream lifetime: a plan orders a launch on a new stream after its previous

@@ -305,6 +305,35 @@ def test_plan_task_sizing():
         small.timer_enable(4)
 
 
+def test_plan_task_counts_pinned():
+    """gs_plan_task_units / gs_plan_n_tasks are public metadata that no kernel acts on: the
+    plan counts its tasks without building a table.  The literals are the values the parent
+    commit's library (which still built the segment / task table) returned for the same
+    plans, as (task_units, n_tasks) for a task_units request of 0 and of 512."""
+    from distributed_training_amd.multi_tensor import TensorListPlan
+    from distributed_training_amd.resnet import MODELS
+    from tests._ema_common import LIST_A, LIST_B
+
+    cpu = torch.device("cpu")
+    cases = [
+        ([1], (256, 1), (512, 1)),
+        ([4099], (256, 5), (512, 3)),
+        (LIST_A, (256, 47), (512, 25)),
+        (LIST_B, (256, 4), (512, 4)),
+        # 20000 elements exceed a task either way: the tensor owns ceil(units / task_units) tasks
+        ([10, 20000, 7, 3000, 2049, 2048], (256, 30), (512, 17)),
+        # 150 tensors of one (even-padded) unit fit a task by size: the 64-tensor cap cuts them
+        ([4] * 150, (256, 3), (512, 3)),
+        ([p.numel() for p in MODELS["resnet50"]().parameters()], (3328, 1992), (512, 12511)),
+    ]
+    for sizes, auto, pinned in cases:
+        for req, want in ((0, auto), (512, pinned)):
+            plan = TensorListPlan(sizes, cpu, task_units=req)
+            assert (plan.task_units, plan.n_tasks) == want, (sizes[:6], req)
+    odd = TensorListPlan(LIST_A, cpu, task_units=301)  # an odd request rounds up to even
+    assert (odd.task_units, odd.n_tasks) == (302, 40)
+
+
 def test_host_threads_bitwise():
     """The host backend's threaded loops (gs_set_host_threads) give the same bits
     as one thread: every op is elementwise, the split only changes who computes."""
