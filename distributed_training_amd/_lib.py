@@ -127,6 +127,12 @@ SIGNATURES = {
     "gs_add_relu_fwd": (_c_int, [_vp, _vp, _c_i64, _vp]),
     "gs_relu_maxpool_fwd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
     "gs_maxpool_bwd": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
+    "gs_relu_mask_fwd": (_c_int, [_vp, _vp, _c_i64, _vp]),
+    "gs_add_relu_mask_fwd": (_c_int, [_vp, _vp, _vp, _c_i64, _vp]),
+    "gs_relu_maxpool_mask_fwd": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
+    "gs_bn_bwd_reduce_bits": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _vp]),
+    "gs_bn_bwd_reduce_fork_bits": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _vp]),
+    "gs_bn_bwd_dx_bits": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_int, _vp]),
     "gs_bn_infer_act": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_d, _c_int, _vp, _c_i64, _c_int, _vp]),
     "gs_bn_infer_relu_maxpool": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_d, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
     "gs_eval_accumulate": (_c_int, [_c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _p_i32, _c_int, _c_i64,

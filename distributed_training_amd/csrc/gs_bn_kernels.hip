@@ -24,6 +24,10 @@
 // pair: relu_maxpool_fwd_kernel (ReLU taken while pooling, a byte per output for
 // the winner) and maxpool_bwd_kernel (dx written once from those bytes).
 //
+// The *_bits / *_mask entries move the ReLU mask as one bit per element instead of the bf16 y: the forward
+// tails (relu, add + relu, the stem's pool) write one byte per 16-B vector while they hold it, the backward
+// passes load that byte where they loaded the vector of y (2 B an element become 0.125 B).
+//
 // Inference (gs_bn_infer_act, gs_bn_infer_relu_maxpool): a BatchNorm in evaluation is a per-channel
 // affine map, so BatchNorm + add + ReLU is one pass on the same (channel tile x row-block) grid: a thread
 // forms s and t of its 8 channels once from the running statistics and streams rows, kBnUnroll in flight.
@@ -156,6 +160,24 @@ __device__ __forceinline__ void relu_mask(float (&g)[8], const bu4& yv) {
   for (int i = 0; i < 8; ++i) g[i] = yf[i] <= 0.f ? 0.f : g[i];
 }
 
+// Where the ReLU mask comes from: nowhere, the saved bf16 output y, or one bit per element
+// (byte i of the mask belongs to the 16-B vector i, bit j set iff !(v[8 i + j] <= 0)).
+enum : int { kMaskNone = 0, kMaskY = 1, kMaskBits = 2 };
+
+// the same g from the vector's mask byte: a cleared bit gives +0, a set bit passes dy
+__device__ __forceinline__ void relu_mask_bits(float (&g)[8], uint32_t mb) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) g[i] = (mb >> i) & 1u ? g[i] : 0.f;
+}
+
+// the mask byte of 8 values: bit j = !(f[j] <= 0), relu_mask()'s predicate (a NaN sets it, +-0 clear it)
+__device__ __forceinline__ uint8_t mask_byte(const float (&f)[8]) {
+  uint32_t mb = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) mb |= (f[j] <= 0.f ? 0u : 1u) << j;
+  return static_cast<uint8_t>(mb);
+}
+
 // dy = dy_a + dy_b as ATen's bf16 add forms it: the sum in fp32, rounded once to bf16
 __device__ __forceinline__ void fork_sum(float (&g)[8], const bu4& bv) {
   float b[8];
@@ -166,11 +188,15 @@ __device__ __forceinline__ void fork_sum(float (&g)[8], const bu4& bv) {
 
 // ---- pass 1: per-workgroup partial sums of g and g * xhat (and g itself) ----
 // FORK: the gradient arrives as the two halves of a fork (dy, dy2) and is summed here
-template <bool RELU, bool WRITE_G, bool FORK>
-__global__ void __launch_bounds__(kBlock)
+// MASK: kMaskY reads y, kMaskBits one byte of mask per vector where kMaskY loads the vector of y
+// The plain reduce from bits is asked for 5 waves per SIMD, what the same pass from y has: it reaches them at
+// 96 VGPRs without scratch, and lands a few registers above without the bound.
+template <int MASK, bool WRITE_G, bool FORK>
+__global__ void __launch_bounds__(kBlock, (MASK == kMaskBits && !WRITE_G) ? 5 : 1)
 bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, const uint16_t* __restrict__ dy2,
-                     const uint16_t* __restrict__ y, uint16_t* __restrict__ gout, const float* __restrict__ mean,
-                     float* __restrict__ ws, int64_t R, int C, int tx_log2, int64_t rpb) {
+                     const uint16_t* __restrict__ y, const uint8_t* __restrict__ mask, uint16_t* __restrict__ gout,
+                     const float* __restrict__ mean, float* __restrict__ ws, int64_t R, int C, int tx_log2,
+                     int64_t rpb) {
   constexpr int U = FORK ? kBnForkUnroll : kBnUnroll;
   __shared__ float s_red[kBlock * 16];  // [ty][F], F = 16 * tx: (channel, {sum g, sum g*(x-mean)})
   __shared__ double s_grp[kBlock];      // [ty / 16][F]
@@ -191,12 +217,13 @@ bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict_
     m[i] = active ? mean[c0 + i] : 0.f;
   }
   // one row's vector: sum g, sum g * (x - mean); invstd scales the second sum once, after the dx pass's fold
-  auto body = [&](const bu4& xv, const bu4& dv, const bu4& bv, const bu4& yv, int64_t off) {
+  auto body = [&](const bu4& xv, const bu4& dv, const bu4& bv, const bu4& yv, uint32_t mb, int64_t off) {
     float xf[8], g[8];
     unpack8(xv, xf);
     unpack8(dv, g);
     if constexpr (FORK) fork_sum(g, bv);
-    if constexpr (RELU) relu_mask(g, yv);
+    if constexpr (MASK == kMaskY) relu_mask(g, yv);
+    if constexpr (MASK == kMaskBits) relu_mask_bits(g, mb);
     if constexpr (WRITE_G) st16(gout + off, pack8_exact(g));
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -210,22 +237,29 @@ bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict_
     int64_t off = r * C + c0;
     for (; r + (U - 1) * ty < r1; r += U * ty, off += U * step) {
       bu4 xv[U], dv[U], bv[U] = {}, yv[U] = {};
+      uint32_t mb[U] = {};
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         xv[k] = ld16<false>(x + off + k * step);  // read again by the dx pass
         dv[k] = ld16<GS_BN_NT && WRITE_G>(dy + off + k * step);
         if constexpr (FORK) bv[k] = ld16<GS_BN_NT>(dy2 + off + k * step);
-        if constexpr (RELU) yv[k] = ld16<GS_BN_NT && WRITE_G>(y + off + k * step);
+        if constexpr (MASK == kMaskY) yv[k] = ld16<GS_BN_NT && WRITE_G>(y + off + k * step);
+        if constexpr (MASK == kMaskBits) mb[k] = mask[(off + k * step) >> 3];
       }
+      // every load of the step is issued before its first use: left to itself the scheduler trades the loads
+      // in flight for registers here (one load, one wait), which costs more than the mask saves
+      if constexpr (MASK == kMaskBits) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int k = 0; k < U; ++k) body(xv[k], dv[k], bv[k], yv[k], off + k * step);
+      for (int k = 0; k < U; ++k) body(xv[k], dv[k], bv[k], yv[k], mb[k], off + k * step);
     }
     for (; r < r1; r += ty, off += step) {
       bu4 bv = {0u, 0u, 0u, 0u}, yv = {0u, 0u, 0u, 0u};
+      uint32_t mb = 0;
       const bu4 xv = ld16<false>(x + off), dv = ld16<false>(dy + off);
       if constexpr (FORK) bv = ld16<false>(dy2 + off);
-      if constexpr (RELU) yv = ld16<false>(y + off);
-      body(xv, dv, bv, yv, off);
+      if constexpr (MASK == kMaskY) yv = ld16<false>(y + off);
+      if constexpr (MASK == kMaskBits) mb = mask[off >> 3];
+      body(xv, dv, bv, yv, mb, off);
     }
   }
   // fold over the ty rows of the workgroup in a fixed order: 16 rows per thread, then the groups.
@@ -256,10 +290,10 @@ bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict_
 }
 
 // ---- pass 2: fold the partials, dx, and (row-block 0) grad_weight / grad_bias ----
-template <bool RELU>
+template <int MASK>
 __global__ void __launch_bounds__(kBlock)
 bn_bwd_dx_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
-                 const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ weight,
+                 const uint8_t* __restrict__ mask, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ weight,
                  const float* __restrict__ ws, int P, uint16_t* __restrict__ dx, float* __restrict__ gw,
                  float* __restrict__ gb, int64_t R, int C, int tx_log2, int64_t rpb, double inv_R) {
   __shared__ double s_fold[kBlock * 4];       // [groups][F4][4], F4 = 4 * tx float4 per partial row of the tile
@@ -311,11 +345,12 @@ bn_bwd_dx_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy
     m1[i] = static_cast<float>(s_sum[tx_i * 16 + 2 * i] * inv_R);
     k2[i] = static_cast<float>(static_cast<double>(is) * is * s_sum[tx_i * 16 + 2 * i + 1] * inv_R);
   }
-  auto body = [&](const bu4& xv, const bu4& dv, const bu4& yv, int64_t off) {
+  auto body = [&](const bu4& xv, const bu4& dv, const bu4& yv, uint32_t mb, int64_t off) {
     float xf[8], g[8];
     unpack8(xv, xf);
     unpack8(dv, g);
-    if constexpr (RELU) relu_mask(g, yv);
+    if constexpr (MASK == kMaskY) relu_mask(g, yv);
+    if constexpr (MASK == kMaskBits) relu_mask_bits(g, mb);
 #pragma unroll
     for (int i = 0; i < 8; ++i) g[i] = a[i] * fmaf(m[i] - xf[i], k2[i], g[i] - m1[i]);
     st16(dx + off, pack8_dx(g));
@@ -327,50 +362,69 @@ bn_bwd_dx_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy
   int64_t off = r * C + c0;
   for (; r + (kBnUnroll - 1) * ty < r1; r += kBnUnroll * ty, off += kBnUnroll * step) {
     bu4 xv[kBnUnroll], dv[kBnUnroll], yv[kBnUnroll] = {};
+    uint32_t mb[kBnUnroll] = {};
 #pragma unroll
     for (int k = 0; k < kBnUnroll; ++k) {
       xv[k] = ld16<GS_BN_NT>(x + off + k * step);
       dv[k] = ld16<GS_BN_NT>(dy + off + k * step);
-      if constexpr (RELU) yv[k] = ld16<GS_BN_NT>(y + off + k * step);
+      if constexpr (MASK == kMaskY) yv[k] = ld16<GS_BN_NT>(y + off + k * step);
+      if constexpr (MASK == kMaskBits) mb[k] = mask[(off + k * step) >> 3];
     }
+    if constexpr (MASK == kMaskBits) __builtin_amdgcn_sched_barrier(0);  // as in the reduce pass
 #pragma unroll
-    for (int k = 0; k < kBnUnroll; ++k) body(xv[k], dv[k], yv[k], off + k * step);
+    for (int k = 0; k < kBnUnroll; ++k) body(xv[k], dv[k], yv[k], mb[k], off + k * step);
   }
   for (; r < r1; r += ty, off += step) {
     bu4 yv = {0u, 0u, 0u, 0u};
+    uint32_t mb = 0;
     const bu4 xv = ld16<false>(x + off), dv = ld16<false>(dy + off);
-    if constexpr (RELU) yv = ld16<false>(y + off);
-    body(xv, dv, yv, off);
+    if constexpr (MASK == kMaskY) yv = ld16<false>(y + off);
+    if constexpr (MASK == kMaskBits) mb = mask[off >> 3];
+    body(xv, dv, yv, mb, off);
   }
 }
 
+// relu_ (= clamp_min_(0)): a NaN stays, everything not above 0 (-0 too) becomes +0
+__device__ __forceinline__ float relu1(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
+
 // ---- forward tail of a residual block: t = relu(t + identity), in place ----
 // the sum in fp32 rounded once to bf16 (ATen's add_), then NaN ? NaN : max(., 0) (relu_ = clamp_min_)
+// ADD = false: the tail of a plain BatchNorm + ReLU, t = relu(t) as relu_ forms it (relu1).
+// MASK: the mask byte of every vector of the result is written as well (the backward's kMaskBits).
+template <bool ADD, bool MASK>
 __global__ void __launch_bounds__(kBlock)
-add_relu_fwd_kernel(uint16_t* __restrict__ t, const uint16_t* __restrict__ id, int64_t nvec) {
+add_relu_fwd_kernel(uint16_t* __restrict__ t, const uint16_t* __restrict__ id, uint8_t* __restrict__ mask,
+                    int64_t nvec) {
   const int64_t base = static_cast<int64_t>(blockIdx.x) * (kBlock * kBnUnroll) + threadIdx.x;
-  bu4 a[kBnUnroll], b[kBnUnroll];
+  bu4 a[kBnUnroll], b[kBnUnroll] = {};
 #pragma unroll
   for (int k = 0; k < kBnUnroll; ++k) {
     const int64_t i = base + k * kBlock;
     if (i < nvec) {
       a[k] = ld16<false>(t + i * 8);
-      b[k] = ld16<false>(id + i * 8);
+      if constexpr (ADD) b[k] = ld16<false>(id + i * 8);
     }
   }
 #pragma unroll
   for (int k = 0; k < kBnUnroll; ++k) {
     const int64_t i = base + k * kBlock;
     if (i < nvec) {
-      float af[8], bf[8];
+      float af[8];
       unpack8(a[k], af);
-      unpack8(b[k], bf);
+      if constexpr (ADD) {
+        float bf[8];
+        unpack8(b[k], bf);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float s = __uint_as_float(to_bf16(af[j] + bf[j]) << 16);
-        af[j] = s != s ? s : fmaxf(s, 0.f);
+        for (int j = 0; j < 8; ++j) {
+          const float s = __uint_as_float(to_bf16(af[j] + bf[j]) << 16);
+          af[j] = s != s ? s : fmaxf(s, 0.f);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) af[j] = relu1(af[j]);
       }
       st16(t + i * 8, pack8_exact(af));
+      if constexpr (MASK) mask[i] = mask_byte(af);
     }
   }
 }
@@ -379,15 +433,15 @@ add_relu_fwd_kernel(uint16_t* __restrict__ t, const uint16_t* __restrict__ id, i
 // NHWC bf16, a thread owns 8 channels of one pixel (C = 64: one 128-B line per pixel, 8 threads).
 // Window of output (oh, ow): rows 2 oh - 1 .. 2 oh + 1, columns 2 ow - 1 .. 2 ow + 1, clipped.
 
-// relu_ (= clamp_min_(0)): a NaN stays, everything not above 0 (-0 too) becomes +0
-__device__ __forceinline__ float relu1(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
-
 // pooled = max over the window of relu(y), idx = the winner's position 3 * kh + kw in the unclipped
 // window.  Scanned rows outer, columns inner; a later value wins only if it is > the current one or
 // is NaN (ATen's max_pool_forward_nhwc): ties keep the first, the last NaN of the window wins.
+// MASK: window positions 4, 5, 7, 8 are the 2 x 2 quad of input pixels (2 oh + dh, 2 ow + dw); the quads
+// partition the input, so the thread writes those pixels' mask bytes (of the un-ReLU'd y) exactly once.
+template <bool MASK>
 __global__ void __launch_bounds__(kBlock)
 relu_maxpool_fwd_kernel(const uint16_t* __restrict__ y, uint16_t* __restrict__ pooled, uint8_t* __restrict__ idx,
-                        int64_t nvec, int H, int W, int OH, int OW, int V) {
+                        uint8_t* __restrict__ mask, int64_t nvec, int H, int W, int OH, int OW, int V) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i >= nvec) return;
   const int cv = static_cast<int>(i % V);
@@ -421,6 +475,10 @@ relu_maxpool_fwd_kernel(const uint16_t* __restrict__ y, uint16_t* __restrict__ p
   for (int k = 0; k < 9; ++k) {
     float f[8];
     unpack8(in[k], f);
+    if constexpr (MASK) {
+      if ((k == 4 || k == 5 || k == 7 || k == 8) && ok[k])
+        mask[((n * H + h0 + k / 3) * W + w0 + k % 3) * V + cv] = mask_byte(f);
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float v = relu1(f[j]);
@@ -728,13 +786,15 @@ int pool_geom(const std::string& w, int64_t N, int H, int W, int C, PoolGeom* g)
   return GS_OK;
 }
 
-// dy_b != NULL: the fork form (g_out required); the checks of both entries
-int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, const void* y, void* g_out,
-              const float* mean, float* ws, int64_t ws_floats, int64_t R, int C, void* stream) {
+// dy_b != NULL: the fork form (g_out required); the checks of all four entries.  bits: the mask comes
+// from `mask` (R * C / 8 bytes, any alignment, required) and y is NULL.
+int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, const void* y, bool bits,
+              const void* mask, void* g_out, const float* mean, float* ws, int64_t ws_floats, int64_t R, int C,
+              void* stream) {
   const std::string w(who);
   GS_TRY_RET(check_shape(R, C));
-  GS_CHECK_ARG(x && dy && mean && ws, w + ": null pointer");
-  GS_CHECK_ARG(!g_out || y || dy_b, w + ": g_out needs y");
+  GS_CHECK_ARG(x && dy && mean && ws && (!bits || mask), w + ": null pointer");
+  GS_CHECK_ARG(!g_out || y || mask || dy_b, w + ": g_out needs y");
   GS_CHECK_ARG(!dy_b || g_out, w + ": two gradients need g_out");
   GS_CHECK_ARG(aligned16(x) && aligned16(dy) && aligned16(dy_b) && aligned16(y) && aligned16(g_out) && aligned16(ws),
                w + ": pointers must be 16-byte aligned");
@@ -744,6 +804,7 @@ int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, 
                      !overlap(g_out, y, bytes),
                  w + ": g_out overlaps an input");
   }
+  GS_CHECK_ARG(!overlap(g_out, R * C * 2, mask, R * C / 8), w + ": g_out overlaps the mask");
   const BnGeom g = bn_geom(R, C);
   GS_CHECK_ARG(ws_floats >= static_cast<int64_t>(g.P) * C * 2, w + ": workspace too small");
   const dim3 grid(g.ctiles, g.P), block(kBlock);
@@ -752,15 +813,19 @@ int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, 
   const uint16_t* dp = static_cast<const uint16_t*>(dy);
   const uint16_t* bp = static_cast<const uint16_t*>(dy_b);
   const uint16_t* yp = static_cast<const uint16_t*>(y);
+  const uint8_t* mp = static_cast<const uint8_t*>(mask);
   uint16_t* gp = static_cast<uint16_t*>(g_out);
-#define GS_BN_REDUCE(RELU, WRITE_G, FORK)                                                                        \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<RELU, WRITE_G, FORK>), grid, block, 0, s, xp, dp, bp, yp, gp, mean, ws, R, \
-                     C, g.tx_log2, g.rpb)
-  if (bp && yp) GS_BN_REDUCE(true, true, true);
-  else if (bp) GS_BN_REDUCE(false, true, true);
-  else if (gp) GS_BN_REDUCE(true, true, false);
-  else if (yp) GS_BN_REDUCE(true, false, false);
-  else GS_BN_REDUCE(false, false, false);
+#define GS_BN_REDUCE(MASK, WRITE_G, FORK)                                                                            \
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<MASK, WRITE_G, FORK>), grid, block, 0, s, xp, dp, bp, yp, mp, gp, mean, ws, \
+                     R, C, g.tx_log2, g.rpb)
+  if (mp && bp) GS_BN_REDUCE(kMaskBits, true, true);
+  else if (mp && gp) GS_BN_REDUCE(kMaskBits, true, false);
+  else if (mp) GS_BN_REDUCE(kMaskBits, false, false);
+  else if (bp && yp) GS_BN_REDUCE(kMaskY, true, true);
+  else if (bp) GS_BN_REDUCE(kMaskNone, true, true);
+  else if (gp) GS_BN_REDUCE(kMaskY, true, false);
+  else if (yp) GS_BN_REDUCE(kMaskY, false, false);
+  else GS_BN_REDUCE(kMaskNone, false, false);
 #undef GS_BN_REDUCE
   HIP_RET(hipGetLastError());
   return GS_OK;
@@ -771,71 +836,151 @@ int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, 
 
 extern "C" int gs_bn_bwd_reduce(const void* x, const void* dy, const void* y, void* g_out, const float* mean,
                                 float* ws, int64_t ws_floats, int64_t R, int C, void* stream) {
-  return bn_reduce("gs_bn_bwd_reduce", x, dy, nullptr, y, g_out, mean, ws, ws_floats, R, C, stream);
+  return bn_reduce("gs_bn_bwd_reduce", x, dy, nullptr, y, false, nullptr, g_out, mean, ws, ws_floats, R, C, stream);
+}
+
+extern "C" int gs_bn_bwd_reduce_bits(const void* x, const void* dy, const void* mask, void* g_out, const float* mean,
+                                     float* ws, int64_t ws_floats, int64_t R, int C, void* stream) {
+  return bn_reduce("gs_bn_bwd_reduce_bits", x, dy, nullptr, nullptr, true, mask, g_out, mean, ws, ws_floats, R, C,
+                   stream);
 }
 
 extern "C" int gs_bn_bwd_reduce_fork(const void* x, const void* dy_a, const void* dy_b, const void* y, void* g_out,
                                      const float* mean, float* ws, int64_t ws_floats, int64_t R, int C,
                                      void* stream) {
-  return bn_reduce("gs_bn_bwd_reduce_fork", x, dy_a, dy_b, y, g_out, mean, ws, ws_floats, R, C, stream);
+  return bn_reduce("gs_bn_bwd_reduce_fork", x, dy_a, dy_b, y, false, nullptr, g_out, mean, ws, ws_floats, R, C,
+                   stream);
 }
 
-extern "C" int gs_bn_bwd_dx(const void* x, const void* dy, const void* y, const float* mean, const float* invstd,
-                            const float* weight, const float* ws, int64_t ws_floats, void* dx, float* grad_weight,
-                            float* grad_bias, int64_t R, int C, void* stream) {
+extern "C" int gs_bn_bwd_reduce_fork_bits(const void* x, const void* dy_a, const void* dy_b, const void* mask,
+                                          void* g_out, const float* mean, float* ws, int64_t ws_floats, int64_t R,
+                                          int C, void* stream) {
+  return bn_reduce("gs_bn_bwd_reduce_fork_bits", x, dy_a, dy_b, nullptr, true, mask, g_out, mean, ws, ws_floats, R, C,
+                   stream);
+}
+
+namespace gs {
+namespace {
+
+// bits: the mask comes from `mask` (required, any alignment, overlaps neither dx) and y is NULL
+int bn_dx(const std::string& w, const void* x, const void* dy, const void* y, bool bits, const void* mask,
+          const float* mean, const float* invstd, const float* weight, const float* ws, int64_t ws_floats, void* dx,
+          float* grad_weight, float* grad_bias, int64_t R, int C, void* stream) {
   GS_TRY_RET(check_shape(R, C));
-  GS_CHECK_ARG(x && dy && mean && invstd && weight && ws && dx && grad_weight && grad_bias,
-               "gs_bn_bwd_dx: null pointer");
+  GS_CHECK_ARG(x && dy && mean && invstd && weight && ws && dx && grad_weight && grad_bias && (!bits || mask),
+               w + ": null pointer");
   GS_CHECK_ARG(aligned16(x) && aligned16(dy) && aligned16(y) && aligned16(dx) && aligned16(ws),
-               "gs_bn_bwd_dx: pointers must be 16-byte aligned");
+               w + ": pointers must be 16-byte aligned");
+  GS_CHECK_ARG(!overlap(dx, R * C * 2, mask, R * C / 8), w + ": dx overlaps the mask");
   const BnGeom g = bn_geom(R, C);
-  GS_CHECK_ARG(ws_floats >= static_cast<int64_t>(g.P) * C * 2, "gs_bn_bwd_dx: workspace too small");
+  GS_CHECK_ARG(ws_floats >= static_cast<int64_t>(g.P) * C * 2, w + ": workspace too small");
   const dim3 grid(g.ctiles, g.P), block(kBlock);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint16_t* xp = static_cast<const uint16_t*>(x);
   const uint16_t* dp = static_cast<const uint16_t*>(dy);
   const uint16_t* yp = static_cast<const uint16_t*>(y);
+  const uint8_t* mp = static_cast<const uint8_t*>(mask);
   uint16_t* op = static_cast<uint16_t*>(dx);
   const double inv_R = 1.0 / static_cast<double>(R);
-  if (yp)
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<true>), grid, block, 0, s, xp, dp, yp, mean, invstd, weight, ws, g.P, op,
-                       grad_weight, grad_bias, R, C, g.tx_log2, g.rpb, inv_R);
-  else
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<false>), grid, block, 0, s, xp, dp, yp, mean, invstd, weight, ws, g.P, op,
-                       grad_weight, grad_bias, R, C, g.tx_log2, g.rpb, inv_R);
+#define GS_BN_DX(MASK)                                                                                              \
+  hipLaunchKernelGGL((bn_bwd_dx_kernel<MASK>), grid, block, 0, s, xp, dp, yp, mp, mean, invstd, weight, ws, g.P, op, \
+                     grad_weight, grad_bias, R, C, g.tx_log2, g.rpb, inv_R)
+  if (mp) GS_BN_DX(kMaskBits);
+  else if (yp) GS_BN_DX(kMaskY);
+  else GS_BN_DX(kMaskNone);
+#undef GS_BN_DX
   HIP_RET(hipGetLastError());
   return GS_OK;
 }
 
-extern "C" int gs_add_relu_fwd(void* t, const void* identity, int64_t n, void* stream) {
-  GS_CHECK_ARG(t && identity && n > 0 && n % 8 == 0, "gs_add_relu_fwd: n > 0, n % 8 == 0 and pointers required");
-  GS_CHECK_ARG(aligned16(t) && aligned16(identity), "gs_add_relu_fwd: pointers must be 16-byte aligned");
+// t = relu(t (+ identity)) in place (+ the mask bytes); identity and mask are optional per entry
+int relu_tail(const std::string& w, void* t, const void* identity, bool add, void* mask, bool bits, int64_t n,
+              void* stream) {
+  GS_CHECK_ARG(t && (!add || identity) && (!bits || mask) && n > 0 && n % 8 == 0,
+               w + ": n > 0, n % 8 == 0 and pointers required");
+  GS_CHECK_ARG(aligned16(t) && aligned16(identity), w + ": pointers must be 16-byte aligned");
+  GS_CHECK_ARG(n <= INT64_MAX / 4, w + ": n too large");
+  GS_CHECK_ARG(!overlap(mask, n / 8, t, n * 2) && !overlap(mask, n / 8, identity, n * 2),
+               w + ": the mask overlaps an activation");
   const int64_t nvec = n / 8;
   const int64_t blocks = (nvec + kBlock * kBnUnroll - 1) / (kBlock * kBnUnroll);
-  GS_CHECK_ARG(blocks <= INT_MAX, "gs_add_relu_fwd: n too large");
-  hipLaunchKernelGGL(add_relu_fwd_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), static_cast<uint16_t*>(t),
-                     static_cast<const uint16_t*>(identity), nvec);
+  GS_CHECK_ARG(blocks <= INT_MAX, w + ": n too large");
+  const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint16_t* tp = static_cast<uint16_t*>(t);
+  const uint16_t* ip = static_cast<const uint16_t*>(identity);
+  uint8_t* mp = static_cast<uint8_t*>(mask);
+  if (!add) hipLaunchKernelGGL((add_relu_fwd_kernel<false, true>), grid, block, 0, s, tp, ip, mp, nvec);
+  else if (bits) hipLaunchKernelGGL((add_relu_fwd_kernel<true, true>), grid, block, 0, s, tp, ip, mp, nvec);
+  else hipLaunchKernelGGL((add_relu_fwd_kernel<true, false>), grid, block, 0, s, tp, ip, mp, nvec);
   HIP_RET(hipGetLastError());
   return GS_OK;
+}
+
+// mask != NULL: the mask bytes of the un-ReLU'd input are written as well (in_vecs bytes)
+int relu_maxpool(const std::string& w, const void* y, void* pooled, void* idx, void* mask, bool bits, int64_t N, int H,
+                 int W, int C, void* stream) {
+  PoolGeom g;
+  GS_TRY_RET(pool_geom(w, N, H, W, C, &g));
+  GS_CHECK_ARG(y && pooled && idx && (!bits || mask), w + ": null pointer");
+  GS_CHECK_ARG(aligned16(y) && aligned16(pooled) && aligned16(idx), w + ": pointers must be 16-byte aligned");
+  const int64_t ib = g.in_vecs * 16, ob = g.out_vecs * 16, xb = g.out_vecs * 8, mb = g.in_vecs;
+  GS_CHECK_ARG(!overlap(y, ib, pooled, ob) && !overlap(y, ib, idx, xb) && !overlap(pooled, ob, idx, xb) &&
+                   !overlap(mask, mb, y, ib) && !overlap(mask, mb, pooled, ob) && !overlap(mask, mb, idx, xb),
+               w + ": buffers overlap");
+  const dim3 grid(static_cast<unsigned>((g.out_vecs + kBlock - 1) / kBlock)), block(kBlock);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint16_t* yp = static_cast<const uint16_t*>(y);
+  uint16_t* pp = static_cast<uint16_t*>(pooled);
+  uint8_t* ip = static_cast<uint8_t*>(idx);
+  uint8_t* mp = static_cast<uint8_t*>(mask);
+  if (mp)
+    hipLaunchKernelGGL((relu_maxpool_fwd_kernel<true>), grid, block, 0, s, yp, pp, ip, mp, g.out_vecs, H, W, g.OH, g.OW,
+                       C / 8);
+  else
+    hipLaunchKernelGGL((relu_maxpool_fwd_kernel<false>), grid, block, 0, s, yp, pp, ip, mp, g.out_vecs, H, W, g.OH,
+                       g.OW, C / 8);
+  HIP_RET(hipGetLastError());
+  return GS_OK;
+}
+
+}  // namespace
+}  // namespace gs
+
+extern "C" int gs_bn_bwd_dx(const void* x, const void* dy, const void* y, const float* mean, const float* invstd,
+                            const float* weight, const float* ws, int64_t ws_floats, void* dx, float* grad_weight,
+                            float* grad_bias, int64_t R, int C, void* stream) {
+  return bn_dx("gs_bn_bwd_dx", x, dy, y, false, nullptr, mean, invstd, weight, ws, ws_floats, dx, grad_weight,
+               grad_bias, R, C, stream);
+}
+
+extern "C" int gs_bn_bwd_dx_bits(const void* x, const void* dy, const void* mask, const float* mean,
+                                 const float* invstd, const float* weight, const float* ws, int64_t ws_floats,
+                                 void* dx, float* grad_weight, float* grad_bias, int64_t R, int C, void* stream) {
+  return bn_dx("gs_bn_bwd_dx_bits", x, dy, nullptr, true, mask, mean, invstd, weight, ws, ws_floats, dx, grad_weight,
+               grad_bias, R, C, stream);
+}
+
+extern "C" int gs_add_relu_fwd(void* t, const void* identity, int64_t n, void* stream) {
+  return relu_tail("gs_add_relu_fwd", t, identity, true, nullptr, false, n, stream);
+}
+
+extern "C" int gs_add_relu_mask_fwd(void* t, const void* identity, void* mask, int64_t n, void* stream) {
+  return relu_tail("gs_add_relu_mask_fwd", t, identity, true, mask, true, n, stream);
+}
+
+extern "C" int gs_relu_mask_fwd(void* t, void* mask, int64_t n, void* stream) {
+  return relu_tail("gs_relu_mask_fwd", t, nullptr, false, mask, true, n, stream);
 }
 
 extern "C" int gs_relu_maxpool_fwd(const void* y, void* pooled, void* idx, int64_t N, int H, int W, int C,
                                    void* stream) {
-  const std::string w("gs_relu_maxpool_fwd");
-  PoolGeom g;
-  GS_TRY_RET(pool_geom(w, N, H, W, C, &g));
-  GS_CHECK_ARG(y && pooled && idx, w + ": null pointer");
-  GS_CHECK_ARG(aligned16(y) && aligned16(pooled) && aligned16(idx), w + ": pointers must be 16-byte aligned");
-  const int64_t ib = g.in_vecs * 16, ob = g.out_vecs * 16, xb = g.out_vecs * 8;
-  GS_CHECK_ARG(!overlap(y, ib, pooled, ob) && !overlap(y, ib, idx, xb) && !overlap(pooled, ob, idx, xb),
-               w + ": buffers overlap");
-  const unsigned blocks = static_cast<unsigned>((g.out_vecs + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(relu_maxpool_fwd_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const uint16_t*>(y), static_cast<uint16_t*>(pooled), static_cast<uint8_t*>(idx),
-                     g.out_vecs, H, W, g.OH, g.OW, C / 8);
-  HIP_RET(hipGetLastError());
-  return GS_OK;
+  return relu_maxpool("gs_relu_maxpool_fwd", y, pooled, idx, nullptr, false, N, H, W, C, stream);
+}
+
+extern "C" int gs_relu_maxpool_mask_fwd(const void* y, void* pooled, void* idx, void* mask, int64_t N, int H, int W,
+                                        int C, void* stream) {
+  return relu_maxpool("gs_relu_maxpool_mask_fwd", y, pooled, idx, mask, true, N, H, W, C, stream);
 }
 
 extern "C" int gs_maxpool_bwd(const void* d_a, const void* d_b, const void* idx, void* dx, int64_t N, int H, int W,

@@ -27,6 +27,12 @@ and keeps a byte per output (no in-place ReLU pass, no int64 indices); backward,
 ``gs_maxpool_bwd`` writes the BatchNorm's dy once from those bytes and the one
 or two pooled gradients (no zero fill, no atomics, no add).
 
+The ReLU mask travels as bits (``GSYNC_BN_MASK``, default ``1``): the forward tail — ``gs_relu_mask_fwd`` in place
+of ``relu_``, ``gs_add_relu_mask_fwd``, ``gs_relu_maxpool_mask_fwd`` — also writes one byte per 8 elements
+(bit j set iff the element is not <= 0), that ``uint8`` tensor of ``numel / 8`` bytes is saved in place of ``y``,
+and ``gs_bn_bwd_reduce_bits`` / ``gs_bn_bwd_reduce_fork_bits`` / ``gs_bn_bwd_dx_bits`` read a byte where they read
+16 of ``y``.  Every result is bit for bit the same; ``GSYNC_BN_MASK=0`` runs the calls described above.
+
 The fused path engages only for: CUDA, training mode, 4-D channels_last bf16
 input, fp32 affine weights, C % 8 == 0, no forward hooks on the module, the
 library loaded, and ``GSYNC_FUSED_BN`` not ``0``.  Everything else (CPU, fp32,
@@ -64,6 +70,11 @@ def _n_partials(R: int, C: int) -> int:
     if P is None:
         P = _partials[(R, C)] = L.check(L.lib().gs_bn_bwd_partials(R, C), "gs_bn_bwd_partials")
     return P
+
+
+def _mask_bits() -> bool:
+    """the ReLU mask as one bit per element instead of the saved bf16 output (``GSYNC_BN_MASK``, default on)"""
+    return os.environ.get("GSYNC_BN_MASK", "1") != "0"
 
 
 def _eligible(bn, x, relu, residual) -> bool:
@@ -148,14 +159,25 @@ class _BnAct(torch.autograd.Function):
             x, weight, bias, bn.running_mean, bn.running_var, True, momentum, bn.eps, torch.backends.cudnn.enabled)
         if not y.is_contiguous(memory_format=_CL):
             raise RuntimeError("fused_bn: batch_norm returned a layout other than its channels_last input's")
-        if residual is not None:
+        mask = None
+        if relu and _mask_bits():
+            mask = torch.empty(y.numel() // 8, dtype=torch.uint8, device=y.device)
+        if residual is not None and mask is not None:
+            L.check(L.lib().gs_add_relu_mask_fwd(y.data_ptr(), residual.data_ptr(), mask.data_ptr(), y.numel(),
+                                                 L.stream_ptr(y.device)), "gs_add_relu_mask_fwd")
+        elif residual is not None:
             L.check(L.lib().gs_add_relu_fwd(y.data_ptr(), residual.data_ptr(), y.numel(), L.stream_ptr(y.device)),
                     "gs_add_relu_fwd")
+        elif mask is not None:
+            L.check(L.lib().gs_relu_mask_fwd(y.data_ptr(), mask.data_ptr(), y.numel(), L.stream_ptr(y.device)),
+                    "gs_relu_mask_fwd")
         elif relu:
             torch.relu_(y)
         ctx.relu = relu
+        ctx.bits = mask is not None
         ctx.has_residual = residual is not None
-        ctx.save_for_backward(x, weight, mean, invstd, y if relu else None)
+        # the mask in place of y (the next convolution keeps y alive anyway)
+        ctx.save_for_backward(x, weight, mean, invstd, mask if mask is not None else (y if relu else None))
         if fork:
             # two tensors over one storage: autograd hands backward their gradients unsummed
             ctx.set_materialize_grads(False)
@@ -181,32 +203,37 @@ class _BnAct(torch.autograd.Function):
         gw = torch.empty_like(weight)
         gb = torch.empty_like(weight)
         lib, stream = L.lib(), L.stream_ptr(x.device)
-        yp = y.data_ptr() if ctx.relu else None
+        yp = y.data_ptr() if ctx.relu else None  # y: the saved output, or its mask bits (ctx.bits)
+        bits = ctx.bits
         g = None
         if dy_b is not None:
             # the fork's sum, the mask and the sums in one pass; g is what ATen's add + threshold_backward left
             g = torch.empty_like(x)
-            L.check(lib.gs_bn_bwd_reduce_fork(x.data_ptr(), dy.data_ptr(), dy_b.data_ptr(), yp, g.data_ptr(),
-                                              mean.data_ptr(), ws.data_ptr(), ws.numel(), R, C, stream),
-                    "gs_bn_bwd_reduce_fork")
+            fn = "gs_bn_bwd_reduce_fork_bits" if bits else "gs_bn_bwd_reduce_fork"
+            L.check(getattr(lib, fn)(x.data_ptr(), dy.data_ptr(), dy_b.data_ptr(), yp, g.data_ptr(), mean.data_ptr(),
+                                     ws.data_ptr(), ws.numel(), R, C, stream), fn)
             dy, yp = g, None
         elif ctx.has_residual:
             g = torch.empty_like(x)
-            L.check(lib.gs_bn_bwd_reduce(x.data_ptr(), dy.data_ptr(), yp, g.data_ptr(), mean.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), R, C, stream), "gs_bn_bwd_reduce")
+            fn = "gs_bn_bwd_reduce_bits" if bits else "gs_bn_bwd_reduce"
+            L.check(getattr(lib, fn)(x.data_ptr(), dy.data_ptr(), yp, g.data_ptr(), mean.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), R, C, stream), fn)
             dy, yp = g, None  # the dx pass reads the masked gradient
         else:
-            L.check(lib.gs_bn_bwd_reduce(x.data_ptr(), dy.data_ptr(), yp, None, mean.data_ptr(), ws.data_ptr(),
-                                         ws.numel(), R, C, stream), "gs_bn_bwd_reduce")
-        L.check(lib.gs_bn_bwd_dx(x.data_ptr(), dy.data_ptr(), yp, mean.data_ptr(), invstd.data_ptr(),
+            fn = "gs_bn_bwd_reduce_bits" if bits else "gs_bn_bwd_reduce"
+            L.check(getattr(lib, fn)(x.data_ptr(), dy.data_ptr(), yp, None, mean.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), R, C, stream), fn)
+        fn = "gs_bn_bwd_dx_bits" if bits and yp is not None else "gs_bn_bwd_dx"
+        L.check(getattr(lib, fn)(x.data_ptr(), dy.data_ptr(), yp, mean.data_ptr(), invstd.data_ptr(),
                                  weight.data_ptr(), ws.data_ptr(), ws.numel(), dx.data_ptr(), gw.data_ptr(),
-                                 gb.data_ptr(), R, C, stream), "gs_bn_bwd_dx")
+                                 gb.data_ptr(), R, C, stream), fn)
         return dx, gw, gb, g if ctx.has_residual else None, None, None, None, None
 
 
 class _BnReluPool(torch.autograd.Function):
     """MaxPool2d(3, 2, 1)(relu(bn(x))): the ReLU is taken while pooling, the BatchNorm output stays
-    un-ReLU'd (its sign is the ReLU mask), the pool keeps one byte per output instead of int64 indices."""
+    un-ReLU'd (its sign is the ReLU mask), the pool keeps one byte per output instead of int64 indices.
+    With ``GSYNC_BN_MASK`` the pool also writes that mask as bits, which are saved in place of the output."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, bn, momentum, fork):
@@ -218,8 +245,15 @@ class _BnReluPool(torch.autograd.Function):
         OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         out = torch.empty((N, C, OH, OW), dtype=y.dtype, device=y.device, memory_format=_CL)
         idx = torch.empty((N, OH, OW, C), dtype=torch.uint8, device=y.device)
-        L.check(L.lib().gs_relu_maxpool_fwd(y.data_ptr(), out.data_ptr(), idx.data_ptr(), N, H, W, C,
-                                            L.stream_ptr(y.device)), "gs_relu_maxpool_fwd")
+        ctx.bits = _mask_bits()
+        if ctx.bits:
+            mask = torch.empty(y.numel() // 8, dtype=torch.uint8, device=y.device)
+            L.check(L.lib().gs_relu_maxpool_mask_fwd(y.data_ptr(), out.data_ptr(), idx.data_ptr(), mask.data_ptr(), N,
+                                                     H, W, C, L.stream_ptr(y.device)), "gs_relu_maxpool_mask_fwd")
+            y = mask
+        else:
+            L.check(L.lib().gs_relu_maxpool_fwd(y.data_ptr(), out.data_ptr(), idx.data_ptr(), N, H, W, C,
+                                                L.stream_ptr(y.device)), "gs_relu_maxpool_fwd")
         ctx.save_for_backward(x, weight, mean, invstd, y, idx)
         if fork:
             ctx.set_materialize_grads(False)
@@ -248,11 +282,13 @@ class _BnReluPool(torch.autograd.Function):
         dx = torch.empty_like(x)
         gw = torch.empty_like(weight)
         gb = torch.empty_like(weight)
-        L.check(lib.gs_bn_bwd_reduce(x.data_ptr(), dy.data_ptr(), y.data_ptr(), None, mean.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), R, C, stream), "gs_bn_bwd_reduce")
-        L.check(lib.gs_bn_bwd_dx(x.data_ptr(), dy.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+        fn = "gs_bn_bwd_reduce_bits" if ctx.bits else "gs_bn_bwd_reduce"  # y: the output, or its mask bits
+        L.check(getattr(lib, fn)(x.data_ptr(), dy.data_ptr(), y.data_ptr(), None, mean.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), R, C, stream), fn)
+        fn = "gs_bn_bwd_dx_bits" if ctx.bits else "gs_bn_bwd_dx"
+        L.check(getattr(lib, fn)(x.data_ptr(), dy.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
                                  weight.data_ptr(), ws.data_ptr(), ws.numel(), dx.data_ptr(), gw.data_ptr(),
-                                 gb.data_ptr(), R, C, stream), "gs_bn_bwd_dx")
+                                 gb.data_ptr(), R, C, stream), fn)
         return dx, gw, gb, None, None, None
 
 

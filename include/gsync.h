@@ -759,6 +759,31 @@ int gs_relu_maxpool_fwd(const void* y, void* pooled, void* idx, int64_t N, int H
  * halves of a fork of the pooled output (ATen's bf16 add). */
 int gs_maxpool_bwd(const void* d_a, const void* d_b, const void* idx, void* dx, int64_t N, int H, int W, int C,
                    void* stream);
+/* The ReLU mask as bits.  For an activation v of n bf16 elements the mask is n / 8 bytes: byte i
+ * belongs to the 16-byte vector i (elements 8 i .. 8 i + 7), bit j is set iff !(v[8 i + j] <= 0)
+ * (a NaN sets it, +-0 and negatives clear it): the predicate of g = dy * [y > 0] above.  The mask
+ * pointer is required, needs no alignment and overlaps no other buffer of the call.
+ *
+ * Forward producers: the arithmetic of their siblings, plus the byte per vector.
+ *   gs_relu_mask_fwd: t = relu(t) in place, bit-identical to ATen's relu_ (a NaN stays, -0 -> +0);
+ *     the mask of the result.
+ *   gs_add_relu_mask_fwd: gs_add_relu_fwd; the mask of the result.
+ *   gs_relu_maxpool_mask_fwd: gs_relu_maxpool_fwd; the mask of the un-ReLU'd input y
+ *     (N * H * W * C / 8 bytes), every byte written exactly once. */
+int gs_relu_mask_fwd(void* t, void* mask, int64_t n, void* stream);
+int gs_add_relu_mask_fwd(void* t, const void* identity, void* mask, int64_t n, void* stream);
+int gs_relu_maxpool_mask_fwd(const void* y, void* pooled, void* idx, void* mask, int64_t N, int H, int W, int C,
+                             void* stream);
+/* Backward consumers: gs_bn_bwd_reduce, gs_bn_bwd_reduce_fork and gs_bn_bwd_dx with the mask
+ * (R * C / 8 bytes) in place of y.  For a mask formed from y every output (the workspace, g_out,
+ * dx, grad_weight, grad_bias) is bit for bit what the y-taking entry writes. */
+int gs_bn_bwd_reduce_bits(const void* x, const void* dy, const void* mask, void* g_out, const float* mean, float* ws,
+                          int64_t ws_floats, int64_t R, int C, void* stream);
+int gs_bn_bwd_reduce_fork_bits(const void* x, const void* dy_a, const void* dy_b, const void* mask, void* g_out,
+                               const float* mean, float* ws, int64_t ws_floats, int64_t R, int C, void* stream);
+int gs_bn_bwd_dx_bits(const void* x, const void* dy, const void* mask, const float* mean, const float* invstd,
+                      const float* weight, const float* ws, int64_t ws_floats, void* dx, float* grad_weight,
+                      float* grad_bias, int64_t R, int C, void* stream);
 
 /* ======================================================================
  * Evaluation: inference BatchNorm fused with its tail, and exact metrics
