@@ -4,11 +4,13 @@
 // threshold_backward, and the in-place add + ReLU at the end of a residual block.
 //
 // An activation is a row-major [R, C] bf16 matrix.  A thread owns 8 consecutive
-// channels (one 16-B access) and walks down the rows; a 256-thread workgroup is
-// tx x ty threads over a channel tile of tx vectors (tx = 8: 64 channels, one
-// 128-B line per row) and ty = 256 / tx rows per step.  The grid is
-// (channel tiles, P row-blocks): wide layers fill the chip from the channel
-// axis, the stem and layer1 from the row axis (bn_geom).
+// channels (one 16-B access) and walks down the rows; a workgroup of the backward
+// passes is tx x ty threads over a channel tile of tx vectors (tx = 32 from C = 256
+// on: 512 contiguous bytes of a row, a wave covers 2 rows) and ty = max(32, 256 / tx)
+// rows per step: 256 threads up to C = 64, 512 at C = 128, 1024 from C = 256 on
+// (bn_geom halves the tile where so large a workgroup would leave CUs without one).
+// The grid is (channel tiles, P row-blocks): wide layers fill the chip from the
+// channel axis, the stem and layer1 from the row axis (bn_geom).
 //
 // HBM-bound streaming, passes over the activation per BN backward:
 //   reduce: x, dy (, y) in (, g out)         dx: x, dy|g (, y) in, dx out
@@ -64,9 +66,17 @@ namespace {
 typedef uint32_t bu4 __attribute__((ext_vector_type(4)));
 typedef float bf4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBnTileVecs = 8;         // vectors (of 8 channels) per channel tile, at most
+// Vectors (of 8 channels) per channel tile of the backward passes, at most: 8, 16 or 32.  A workgroup
+// touches tx * 16 contiguous bytes of a row and rows lie 2 C bytes apart; 512 bytes stream faster than
+// 128.  -DGS_BN_TILE_VECS=8 rebuilds the 8-vector tile in 256-thread workgroups.
+#ifndef GS_BN_TILE_VECS
+#define GS_BN_TILE_VECS 32
+#endif
+constexpr int kBnTileVecs = GS_BN_TILE_VECS;
+static_assert(kBnTileVecs == 8 || kBnTileVecs == 16 || kBnTileVecs == 32, "GS_BN_TILE_VECS: 8, 16 or 32");
+constexpr int kBnMinRows = 32;         // rows per workgroup step, at least: bounds a thread's fp32 chain
 constexpr int kBnMaxP = 512;           // row-blocks, at most
-constexpr int kBnTargetBlocks = 1024;  // 4 workgroups per CU
+constexpr int kBnTargetBlocks = 1024;  // 4 workgroups of 256 threads per CU, or as many waves in larger ones
 constexpr int kBnUnroll = 4;           // rows in flight per thread and stream
 #ifndef GS_BN_FORK_UNROLL
 #define GS_BN_FORK_UNROLL 4
@@ -77,31 +87,50 @@ constexpr int kBnForkUnroll = GS_BN_FORK_UNROLL;  // the same, for the reduce th
 //   P <= ceil(R / ty): a row-block has at least one step of rows;
 //   P <= sqrt(R / 2): the fold (P * P * 8 bytes per channel) stays under half the
 //        bytes streamed (R * 6 per channel), and it is read from L2;
-//   tiles * P near kBnTargetBlocks, a multiple of 256 CUs where it exceeds them.
+//   units * P near kBnTargetBlocks, units = tiles * (threads / 256) the workgroups of a row-block counted
+//        in 256 threads: the resident waves do not depend on the tile's width (a 32-vector tile has a
+//        quarter of the 8-vector tiles, in workgroups four times as large, so P is what the 8-vector
+//        tile gave wherever C / 8 is a power of two);
+//   units * P a multiple of 256 CUs where it exceeds them.
+// The tile: tx = min(kBnTileVecs, pow2ceil(C / 8)) vectors, halved (not below 8) while the grid has fewer
+// workgroups than the 256 CUs although every thread has an unrolled step of rows to stream: a 1024-thread
+// workgroup is alone on its CU, so 128 of them leave half the chip idle, and P cannot grow past sqrt(R / 2)
+// (50176 x 256 and 12544 x 512 of ResNet-50 x 256 run 256 workgroups of a 16-vector tile: DESIGN §3e).
 struct BnGeom {
   int tx_log2;
   int ctiles;
   int P;
-  int64_t rpb;  // rows per row-block
+  int64_t rpb;         // rows per row-block
+  int block = kBlock;  // threads per workgroup: tx * ty
 };
+
+BnGeom bn_geom_tile(int64_t R, int C, int l2) {
+  const int V = C / 8;
+  const int tx = 1 << l2, ty = std::max(kBnMinRows, kBlock / tx);
+  const int block = tx * ty;  // 256 up to tx = 8, then 512, 1024
+  const int64_t ctiles = (V + tx - 1) / tx;
+  int64_t P = std::min<int64_t>(kBnMaxP, (R + ty - 1) / ty);
+  P = std::min<int64_t>(P, static_cast<int64_t>(std::sqrt(0.5 * static_cast<double>(R))));
+  const int64_t units = ctiles * (block / kBlock);
+  P = std::min<int64_t>(P, kBnTargetBlocks / units);
+  P = std::max<int64_t>(P, 1);
+  if (units * P > 256) {
+    const int64_t step = 256 / std::min<int64_t>(256, units & -units);
+    if (P >= step) P -= P % step;
+  }
+  const int64_t rpb = (R + P - 1) / P;
+  P = (R + rpb - 1) / rpb;  // no empty row-block
+  return BnGeom{l2, static_cast<int>(ctiles), static_cast<int>(P), rpb, block};
+}
 
 BnGeom bn_geom(int64_t R, int C) {
   const int V = C / 8;
   int l2 = 0;
   while ((1 << l2) < V && (1 << l2) < kBnTileVecs) ++l2;
-  const int tx = 1 << l2, ty = kBlock / tx;
-  const int64_t ctiles = (V + tx - 1) / tx;
-  int64_t P = std::min<int64_t>(kBnMaxP, (R + ty - 1) / ty);
-  P = std::min<int64_t>(P, static_cast<int64_t>(std::sqrt(0.5 * static_cast<double>(R))));
-  P = std::min<int64_t>(P, kBnTargetBlocks / ctiles);
-  P = std::max<int64_t>(P, 1);
-  if (ctiles * P > 256) {
-    const int64_t step = 256 / std::min<int64_t>(256, ctiles & -ctiles);
-    if (P >= step) P -= P % step;
-  }
-  const int64_t rpb = (R + P - 1) / P;
-  P = (R + rpb - 1) / rpb;  // no empty row-block
-  return BnGeom{l2, static_cast<int>(ctiles), static_cast<int>(P), rpb};
+  BnGeom g = bn_geom_tile(R, C, l2);
+  while (l2 > 3 && static_cast<int64_t>(g.ctiles) * g.P < 256 && g.rpb >= kBnUnroll * kBnMinRows)
+    g = bn_geom_tile(R, C, --l2);
+  return g;
 }
 
 __device__ __forceinline__ uint32_t to_bf16(float f) {
@@ -191,17 +220,19 @@ __device__ __forceinline__ void fork_sum(float (&g)[8], const bu4& bv) {
 // MASK: kMaskY reads y, kMaskBits one byte of mask per vector where kMaskY loads the vector of y
 // The plain reduce from bits is asked for 5 waves per SIMD, what the same pass from y has: it reaches them at
 // 96 VGPRs without scratch, and lands a few registers above without the bound.
-template <int MASK, bool WRITE_G, bool FORK>
-__global__ void __launch_bounds__(kBlock, (MASK == kMaskBits && !WRITE_G) ? 5 : 1)
+// BLOCK = tx * ty threads (bn_geom): a 1024-thread workgroup is 4 waves per SIMD, 128 VGPRs at most, and
+// the only one on its CU; its 72 KiB of LDS are under gfx950's 160 KiB per workgroup.
+template <int BLOCK, int MASK, bool WRITE_G, bool FORK>
+__global__ void __launch_bounds__(BLOCK, (BLOCK == kBlock && MASK == kMaskBits && !WRITE_G) ? 5 : 1)
 bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, const uint16_t* __restrict__ dy2,
                      const uint16_t* __restrict__ y, const uint8_t* __restrict__ mask, uint16_t* __restrict__ gout,
                      const float* __restrict__ mean, float* __restrict__ ws, int64_t R, int C, int tx_log2,
                      int64_t rpb) {
   constexpr int U = FORK ? kBnForkUnroll : kBnUnroll;
-  __shared__ float s_red[kBlock * 16];  // [ty][F], F = 16 * tx: (channel, {sum g, sum g*(x-mean)})
-  __shared__ double s_grp[kBlock];      // [ty / 16][F]
+  __shared__ float s_red[BLOCK * 16];  // [ty][F], F = 16 * tx: (channel, {sum g, sum g*(x-mean)})
+  __shared__ double s_grp[BLOCK];      // [ty / 16][F]
   const int t = threadIdx.x;
-  const int tx = 1 << tx_log2, ty = kBlock >> tx_log2;
+  const int tx = 1 << tx_log2, ty = BLOCK >> tx_log2;
   const int tx_i = t & (tx - 1), ty_i = t >> tx_log2;
   const int v = blockIdx.x * tx + tx_i;
   const bool active = v < (C >> 3);
@@ -262,7 +293,8 @@ bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict_
       body(xv, dv, bv, yv, mb, off);
     }
   }
-  // fold over the ty rows of the workgroup in a fixed order: 16 rows per thread, then the groups.
+  // fold over the ty rows of the workgroup in a fixed order: 16 rows per thread, then the groups
+  // (ty is a multiple of 16 and F = 16 * tx <= BLOCK for every tx: ty / 16 groups of F threads).
   // The folds here and in the dx pass add in fp64 (a few hundred adds per workgroup), so what is
   // left of the summation error is the threads' own fp32 accumulation over their rows.
   const int F = 16 << tx_log2;
@@ -281,7 +313,7 @@ bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict_
   }
   __syncthreads();
   if (t < F) {
-    const int G = kBlock / F;
+    const int G = BLOCK / F;
     double a = 0.0;
     for (int k = 0; k < G; ++k) a += s_grp[k * F + t];
     const int ch = blockIdx.x * (tx * 8) + (t >> 1);
@@ -290,21 +322,22 @@ bn_bwd_reduce_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict_
 }
 
 // ---- pass 2: fold the partials, dx, and (row-block 0) grad_weight / grad_bias ----
-template <int MASK>
-__global__ void __launch_bounds__(kBlock)
+template <int BLOCK, int MASK>
+__global__ void __launch_bounds__(BLOCK)
 bn_bwd_dx_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, const uint16_t* __restrict__ y,
                  const uint8_t* __restrict__ mask, const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ weight,
                  const float* __restrict__ ws, int P, uint16_t* __restrict__ dx, float* __restrict__ gw,
                  float* __restrict__ gb, int64_t R, int C, int tx_log2, int64_t rpb, double inv_R) {
-  __shared__ double s_fold[kBlock * 4];       // [groups][F4][4], F4 = 4 * tx float4 per partial row of the tile
-  __shared__ double s_sum[16 * kBnTileVecs];  // [F]: (channel, {sum g, sum g*(x-mean)})
+  __shared__ double s_fold[BLOCK * 4];        // [groups][F4][4], F4 = 4 * tx float4 per partial row of the tile
+  __shared__ double s_sum[BLOCK / 2];         // [F]: (channel, {sum g, sum g*(x-mean)}), F = 16 * tx <= BLOCK / 2
   const int t = threadIdx.x;
-  const int tx = 1 << tx_log2, ty = kBlock >> tx_log2;
+  const int tx = 1 << tx_log2, ty = BLOCK >> tx_log2;
   const int tx_i = t & (tx - 1), ty_i = t >> tx_log2;
   const int tile_c0 = blockIdx.x * (tx * 8);
   {
     // thread (grp, q) adds float4 q of partials grp, grp + G4, ...; then the groups in order
-    const int F4 = 4 << tx_log2, G4 = kBlock / F4;
+    // (G4 = ty / 4 groups of F4 threads; the second round's 4 * F4 = 16 * tx threads are at most half of BLOCK)
+    const int F4 = 4 << tx_log2, G4 = BLOCK / F4;
     const int q = t & (F4 - 1), grp = t >> (tx_log2 + 2);
     double a[4] = {0.0, 0.0, 0.0, 0.0};
     if (tile_c0 + 2 * q < C) {
@@ -807,7 +840,7 @@ int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, 
   GS_CHECK_ARG(!overlap(g_out, R * C * 2, mask, R * C / 8), w + ": g_out overlaps the mask");
   const BnGeom g = bn_geom(R, C);
   GS_CHECK_ARG(ws_floats >= static_cast<int64_t>(g.P) * C * 2, w + ": workspace too small");
-  const dim3 grid(g.ctiles, g.P), block(kBlock);
+  const dim3 grid(g.ctiles, g.P), block(g.block);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint16_t* xp = static_cast<const uint16_t*>(x);
   const uint16_t* dp = static_cast<const uint16_t*>(dy);
@@ -815,9 +848,26 @@ int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, 
   const uint16_t* yp = static_cast<const uint16_t*>(y);
   const uint8_t* mp = static_cast<const uint8_t*>(mask);
   uint16_t* gp = static_cast<uint16_t*>(g_out);
-#define GS_BN_REDUCE(MASK, WRITE_G, FORK)                                                                            \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<MASK, WRITE_G, FORK>), grid, block, 0, s, xp, dp, bp, yp, mp, gp, mean, ws, \
-                     R, C, g.tx_log2, g.rpb)
+  // the workgroup size follows the tile (bn_geom); the sizes kBnTileVecs rules out are not compiled
+#define GS_BN_REDUCE_B(BLOCK, MASK, WRITE_G, FORK)                                                                    \
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<BLOCK, MASK, WRITE_G, FORK>), grid, block, 0, s, xp, dp, bp, yp, mp, gp, \
+                     mean, ws, R, C, g.tx_log2, g.rpb)
+#define GS_BN_REDUCE(MASK, WRITE_G, FORK)                                 \
+  do {                                                                    \
+    if constexpr (kBnTileVecs >= 32) {                                    \
+      if (g.block == 4 * kBlock) {                                        \
+        GS_BN_REDUCE_B(4 * kBlock, MASK, WRITE_G, FORK);                  \
+        break;                                                            \
+      }                                                                   \
+    }                                                                     \
+    if constexpr (kBnTileVecs >= 16) {                                    \
+      if (g.block == 2 * kBlock) {                                        \
+        GS_BN_REDUCE_B(2 * kBlock, MASK, WRITE_G, FORK);                  \
+        break;                                                            \
+      }                                                                   \
+    }                                                                     \
+    GS_BN_REDUCE_B(kBlock, MASK, WRITE_G, FORK);                          \
+  } while (0)
   if (mp && bp) GS_BN_REDUCE(kMaskBits, true, true);
   else if (mp && gp) GS_BN_REDUCE(kMaskBits, true, false);
   else if (mp) GS_BN_REDUCE(kMaskBits, false, false);
@@ -827,6 +877,7 @@ int bn_reduce(const char* who, const void* x, const void* dy, const void* dy_b, 
   else if (yp) GS_BN_REDUCE(kMaskY, false, false);
   else GS_BN_REDUCE(kMaskNone, false, false);
 #undef GS_BN_REDUCE
+#undef GS_BN_REDUCE_B
   HIP_RET(hipGetLastError());
   return GS_OK;
 }
@@ -874,7 +925,7 @@ int bn_dx(const std::string& w, const void* x, const void* dy, const void* y, bo
   GS_CHECK_ARG(!overlap(dx, R * C * 2, mask, R * C / 8), w + ": dx overlaps the mask");
   const BnGeom g = bn_geom(R, C);
   GS_CHECK_ARG(ws_floats >= static_cast<int64_t>(g.P) * C * 2, w + ": workspace too small");
-  const dim3 grid(g.ctiles, g.P), block(kBlock);
+  const dim3 grid(g.ctiles, g.P), block(g.block);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint16_t* xp = static_cast<const uint16_t*>(x);
   const uint16_t* dp = static_cast<const uint16_t*>(dy);
@@ -882,13 +933,30 @@ int bn_dx(const std::string& w, const void* x, const void* dy, const void* y, bo
   const uint8_t* mp = static_cast<const uint8_t*>(mask);
   uint16_t* op = static_cast<uint16_t*>(dx);
   const double inv_R = 1.0 / static_cast<double>(R);
-#define GS_BN_DX(MASK)                                                                                              \
-  hipLaunchKernelGGL((bn_bwd_dx_kernel<MASK>), grid, block, 0, s, xp, dp, yp, mp, mean, invstd, weight, ws, g.P, op, \
-                     grad_weight, grad_bias, R, C, g.tx_log2, g.rpb, inv_R)
+#define GS_BN_DX_B(BLOCK, MASK)                                                                                     \
+  hipLaunchKernelGGL((bn_bwd_dx_kernel<BLOCK, MASK>), grid, block, 0, s, xp, dp, yp, mp, mean, invstd, weight, ws, \
+                     g.P, op, grad_weight, grad_bias, R, C, g.tx_log2, g.rpb, inv_R)
+#define GS_BN_DX(MASK)                     \
+  do {                                     \
+    if constexpr (kBnTileVecs >= 32) {     \
+      if (g.block == 4 * kBlock) {         \
+        GS_BN_DX_B(4 * kBlock, MASK);      \
+        break;                             \
+      }                                    \
+    }                                      \
+    if constexpr (kBnTileVecs >= 16) {     \
+      if (g.block == 2 * kBlock) {         \
+        GS_BN_DX_B(2 * kBlock, MASK);      \
+        break;                             \
+      }                                    \
+    }                                      \
+    GS_BN_DX_B(kBlock, MASK);              \
+  } while (0)
   if (mp) GS_BN_DX(kMaskBits);
   else if (yp) GS_BN_DX(kMaskY);
   else GS_BN_DX(kMaskNone);
 #undef GS_BN_DX
+#undef GS_BN_DX_B
   HIP_RET(hipGetLastError());
   return GS_OK;
 }
