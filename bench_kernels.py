@@ -253,6 +253,48 @@ def main():
             del tavg
         eplan.close()
         del avg, src16, avg16
+    # the training criterion (gs_xent_fwd + gs_xent_bwd through loss.cross_entropy): forward plus backward
+    # with label smoothing, beside torch's path on the same tensors as autocast runs it (the logits cast to
+    # fp32 first), both from this run.  Latency-bound: the row's point is the time and the launch count.
+    if want("xent"):
+        import torch.nn.functional as F
+
+        from distributed_training_amd.loss import cross_entropy
+
+        def launches(fn):
+            """device kernels (and memsets / copies) one call of fn enqueues, or None without a profiler"""
+            try:
+                from torch.profiler import ProfilerActivity, profile
+
+                fn()
+                torch.cuda.synchronize()
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    fn()
+                    torch.cuda.synchronize()
+                return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+            except Exception:  # noqa: BLE001
+                return None
+
+        for Bx, Kx, dt in ((256, 1000, torch.bfloat16), (100, 10, torch.float32)):
+            zx = (torch.randn(Bx, Kx, device=dev, generator=g) * 3).to(dt).requires_grad_()
+            yx = torch.randint(0, Kx, (Bx,), device=dev, generator=g)
+
+            def fused_step():
+                zx.grad = None
+                cross_entropy(zx, yx, label_smoothing=0.1).backward()
+
+            def torch_step():
+                zx.grad = None
+                F.cross_entropy(zx.float(), yx, label_smoothing=0.1).backward()
+
+            t_ms = timeit(torch_step, args.iters)
+            t_batched = timeit_batched(torch_step, args.iters)
+            t_n = launches(torch_step)
+            f_n = launches(fused_step)
+            f_ms = timeit(fused_step, args.iters)
+            rec("xent_step", 3 * Bx * Kx * zx.element_size(), *f_ms, "libgsync", B=Bx, K=Kx, dtype=str(dt)[6:],
+                label_smoothing=0.1, launches=f_n, torch_median_ms=t_ms[0], torch_avg_ms=t_ms[1],
+                torch_batched_avg_ms=t_batched, torch_launches=t_n, ratio_to_torch=f_ms[0] / t_ms[0])
     if not args.skip_torch and want("lamb"):
         # a LAMB step of the same arithmetic as torch foreach ops, everything on the device
         bp, bm, bv = [p.clone() for p in params], [x.clone() for x in ms], [x.clone() for x in vs]

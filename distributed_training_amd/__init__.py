@@ -10,6 +10,8 @@ Public surface:
                             fused EMA / SWA weight averaging (torch.optim.swa_utils drop-ins)
   Metrics / evaluate        distributed evaluation: exact metrics kept on the device, every dataset
                             sample counted once, the fused inference BatchNorm forward
+  CrossEntropyLoss / cross_entropy  the fused training criterion (label smoothing, fp32 loss, gradient
+                            in the logits' dtype), optionally advancing a Metrics on the device
   compat.deepspeed / compat.colossalai  API shims for the other two trainers
 """
 from . import _lib  # noqa: F401
@@ -18,6 +20,7 @@ from .ddp import DDP, DistributedDataParallel, GradBucket, compute_bucket_assign
 from .graphs import CapturedStep  # noqa: F401
 from .ema import AveragedModel, ShardedAveragedModel, get_ema_multi_avg_fn, get_swa_multi_avg_fn  # noqa: F401
 from .evaluation import Metrics, evaluate  # noqa: F401
+from .loss import CrossEntropyLoss, cross_entropy  # noqa: F401
 from .flatten import copy_flat_to, flatten_dense_tensors, unflatten_dense_tensors  # noqa: F401
 from .multi_tensor import TensorListPlan  # noqa: F401
 from .optim import FusedAdam, FusedAdamW, FusedLAMB, FusedLARS, FusedSGD, clip_grad_norm_  # noqa: F401

@@ -137,6 +137,10 @@ SIGNATURES = {
     "gs_bn_infer_relu_maxpool": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_d, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
     "gs_eval_accumulate": (_c_int, [_c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _p_i32, _c_int, _c_i64,
                                     _vp, _vp, _vp]),
+    "gs_xent_fwd": (_c_int, [_c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f, _vp, _vp, _p_i32, _c_int,
+                             _vp, _vp]),
+    "gs_xent_bwd": (_c_int, [_c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f, _c_int, _vp, _vp, _vp, _vp,
+                             _c_i64, _vp]),
     "gs_clip_coef":(_c_int, [_c_int, _vp, _c_f, _c_f, _vp, _vp, _vp]),
     "gs_unscale_check": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),
     "gs_sgd_step": (

@@ -296,6 +296,55 @@ int hip_eval_accumulate(const void* logits, int dt, const int64_t* labels, int64
 int host_eval_accumulate(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
                          int64_t n_valid, const EvalTopk& topk, int64_t ignore_index, void* ws, void* acc);
 
+// ---- training criterion (gs_xent_fwd / gs_xent_bwd: gs_loss_kernels.hip / gs_host.cpp) ----
+// A row's forward result: what the backward needs to rebuild the softmax, and the row's code
+// (EvalRow's rules).  A skipped or bad row is {0, 0, 0, code}; a NaN row is all NaN.
+struct XentRow {
+  float loss, m, logS;
+  int32_t code;
+};
+static_assert(sizeof(XentRow) == 16, "XentRow layout");
+struct XentRed {
+  float loss_sum, loss_mean;
+  int32_t counted, bad;
+};
+static_assert(sizeof(XentRed) == 16, "XentRed layout");
+constexpr int kXentNone = 0, kXentMean = 1, kXentSum = 2;
+// the smoothed loss of a counted row from nll = (m - z_y) + logS and T = sum z_j; every
+// multiply and add is its own rounding (-ffp-contract=off).  eps == 0: T is not looked at.
+GS_HD inline float xent_loss(float m, float logS, float zy, float T, int K, float eps) {
+  const float nll = (m - zy) + logS;
+  if (eps == 0.f) return nll;
+  const float smooth = (m + logS) - T / static_cast<float>(K);
+  return (1.f - eps) * nll + eps * smooth;
+}
+// the reduced loss from the fp64 total of the counted rows' losses
+GS_HD inline XentRed xent_reduce(double total, int64_t counted, int64_t bad) {
+  XentRed r;
+  const float nanf32 = static_cast<float>(NAN);
+  r.loss_sum = bad ? nanf32 : static_cast<float>(total);
+  r.loss_mean = (bad || counted == 0) ? nanf32 : static_cast<float>(total / static_cast<double>(counted));
+  r.counted = static_cast<int32_t>(counted);
+  r.bad = static_cast<int32_t>(bad);
+  return r;
+}
+// a gradient element: c * (p - q), p = expf((z - m) - logS), each step rounded once
+GS_HD inline float xent_grad(float z, float m, float logS, float q, float c) {
+  const float p = expf((z - m) - logS);
+  return c * (p - q);
+}
+int hip_xent_fwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
+                 int64_t ignore_index, float eps, void* rows, void* red, const EvalTopk& topk, void* acc,
+                 void* stream);
+int host_xent_fwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
+                  int64_t ignore_index, float eps, void* rows, void* red, const EvalTopk& topk, void* acc);
+int hip_xent_bwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride, float eps,
+                 int reduction, const void* rows, const void* red, const float* grad_out, void* dlogits,
+                 int64_t d_row_stride, void* stream);
+int host_xent_bwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride, float eps,
+                  int reduction, const void* rows, const void* red, const float* grad_out, void* dlogits,
+                  int64_t d_row_stride);
+
 // Deferred watchdog marks (gs_comm.cpp): a consumer plan's launch carries the mark of
 // the collectives deferred to it.  comm_mark_take: 0 = nothing to do (the
 // communicator is gone or not watching), 1 = carry *ev as the launch's stop event

@@ -21,6 +21,7 @@
 #include <climits>
 
 #include "gs_common.h"
+#include "gs_wave.h"
 
 namespace gs {
 namespace {
@@ -31,37 +32,6 @@ namespace {
     if (_e != hipSuccess)                                                           \
       return fail(GS_EHIP, std::string(#expr " failed: ") + hipGetErrorString(_e)); \
   } while (0)
-
-constexpr int kWave = 64;
-constexpr int kRowsPerBlock = kBlock / kWave;
-constexpr int kTreeLevels = 26;  // a lane adds at most 2^25 terms: K <= 2^30 (checked by the entry)
-
-template <int DT>
-__device__ __forceinline__ float ld_logit(const void* base, int64_t i) {
-  if constexpr (DT == GS_F32) {
-    return static_cast<const float*>(base)[i];
-  } else if constexpr (DT == GS_BF16) {
-    return __uint_as_float(static_cast<uint32_t>(static_cast<const uint16_t*>(base)[i]) << 16);
-  } else {
-    return static_cast<float>(static_cast<const _Float16*>(base)[i]);
-  }
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v = v + __shfl_xor(v, o, kWave);  // both partners form a + b: all lanes agree
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
 
 template <int DT>
 __global__ void __launch_bounds__(kBlock)
@@ -89,11 +59,8 @@ eval_rows_kernel(const void* __restrict__ logits, const int64_t* __restrict__ la
     if (lane == 0) ws[row] = EvalRow{__uint_as_float(0x7FC00000u), kEvalNanRow};
     return;
   }
-  // pass 2: the pairwise sum of the lane's terms (acc[l] holds a finished subtree of 2^l terms
-  // where bit l of the count is set), the two counts of the rank
-  float acc[kTreeLevels];
-#pragma unroll
-  for (int l = 0; l < kTreeLevels; ++l) acc[l] = 0.f;
+  // pass 2: the pairwise sum of the lane's terms (LaneTree), the two counts of the rank
+  LaneTree tree;
   int gt = 0, eq = 0;
   uint32_t cnt = 0;  // wave-uniform: a lane past the row's end adds an exact 0
   for (int j0 = 0; j0 < K; j0 += kWave, ++cnt) {
@@ -105,29 +72,9 @@ eval_rows_kernel(const void* __restrict__ logits, const int64_t* __restrict__ la
       gt += z > zy;
       eq += (z == zy) & (j < y);
     }
-    bool placed = false;
-#pragma unroll
-    for (int l = 0; l < kTreeLevels; ++l) {
-      if (!placed) {
-        if (cnt & (1u << l)) {
-          e = acc[l] + e;
-        } else {
-          acc[l] = e;
-          placed = true;
-        }
-      }
-    }
+    tree.push(e, cnt);
   }
-  // fold what is left, small subtrees first
-  float s = 0.f;
-  bool any = false;
-#pragma unroll
-  for (int l = 0; l < kTreeLevels; ++l) {
-    if (cnt & (1u << l)) {
-      s = any ? acc[l] + s : acc[l];
-      any = true;
-    }
-  }
+  float s = tree.fold(cnt);
   s = wave_sum(s);
   const int rank = wave_sum_i(gt) + wave_sum_i(eq);
   if (lane == 0) ws[row] = EvalRow{eval_loss(m, s, zy), rank};

@@ -463,10 +463,33 @@ int host_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const
   return GS_OK;
 }
 
+// A pairwise sum of terms pushed one by one: a binary counter of finished subtrees, small ones
+// folded first, so at most ceil(log2 n) roundings lie on any path, as in the device's tree
+// (gs_wave.h); its order differs from the device's.
+struct PairSum {
+  float acc[32];
+  // j: how many terms were pushed before this one
+  void push(float e, uint32_t j) {
+    int l = 0;
+    for (; j & (1u << l); ++l) e = acc[l] + e;
+    acc[l] = e;
+  }
+  float fold(uint32_t n) const {
+    float s = 0.f;
+    bool any = false;
+    for (int l = 0; l < 31; ++l) {
+      if (n & (1u << l)) {
+        s = any ? acc[l] + s : acc[l];
+        any = true;
+      }
+    }
+    return s;
+  }
+};
+
 // gs_eval_accumulate on the host: the rules of include/gsync.h row by row.  The sum of the
-// exponentials is pairwise (a binary counter of finished subtrees, small ones folded first), so
-// at most ceil(log2 K) roundings lie on any path, as in the device's tree; its order differs
-// from the device's, the counts do not.
+// exponentials is a PairSum: the losses may differ from the device's by a few ulps, the counts
+// do not.
 template <int DT>
 void host_eval_rows(const void* logits, const int64_t* labels, int64_t B, int K, int64_t row_stride,
                     int64_t n_valid, int64_t ignore_index, EvalRow* ws) {
@@ -493,25 +516,14 @@ void host_eval_rows(const void* logits, const int64_t* labels, int64_t B, int K,
       ws[row] = EvalRow{std::nanf(""), kEvalNanRow};
       continue;
     }
-    float acc[32];
+    PairSum se;
     int rank = 0;
     for (int j = 0; j < K; ++j) {
       const float z = ldT<DT>(logits, base + j);
-      float e = expf(z - m);
       rank += (z > zy) || (z == zy && j < y);
-      int l = 0;
-      for (; static_cast<uint32_t>(j) & (1u << l); ++l) e = acc[l] + e;
-      acc[l] = e;
+      se.push(expf(z - m), static_cast<uint32_t>(j));
     }
-    float s = 0.f;
-    bool any = false;
-    for (int l = 0; l < 31; ++l) {
-      if (static_cast<uint32_t>(K) & (1u << l)) {
-        s = any ? acc[l] + s : acc[l];
-        any = true;
-      }
-    }
-    ws[row] = EvalRow{eval_loss(m, s, zy), rank};
+    ws[row] = EvalRow{eval_loss(m, se.fold(static_cast<uint32_t>(K)), zy), rank};
   }
 }
 
@@ -535,6 +547,109 @@ int host_eval_accumulate(const void* logits, int dt, const int64_t* labels, int6
   std::memcpy(&cur, ap + 2, 8);
   cur = cur + total;
   std::memcpy(ap + 2, &cur, 8);
+  return GS_OK;
+}
+
+// gs_xent_fwd on the host: the rules of include/gsync.h row by row, the sums as PairSums.
+template <int DT>
+void host_xent_rows(const void* logits, const int64_t* labels, int64_t B, int K, int64_t row_stride,
+                    int64_t ignore_index, float eps, XentRow* rows, double* nll) {
+  for (int64_t row = 0; row < B; ++row) {
+    const int64_t y = labels[row];
+    nll[row] = 0.0;
+    if (y == ignore_index || y < 0 || y >= K) {
+      rows[row] = XentRow{0.f, 0.f, 0.f, y == ignore_index ? kEvalSkip : kEvalBad};
+      continue;
+    }
+    const int64_t base = row * row_stride;
+    const float zy = ldT<DT>(logits, base + y);
+    float m = -INFINITY;
+    bool nan = false;
+    for (int j = 0; j < K; ++j) {
+      const float z = ldT<DT>(logits, base + j);
+      nan |= z != z;
+      m = z > m ? z : m;
+    }
+    if (nan) {
+      const float q = std::nanf("");
+      rows[row] = XentRow{q, q, q, kEvalNanRow};
+      nll[row] = q;
+      continue;
+    }
+    PairSum se, sz;
+    int rank = 0;
+    for (int j = 0; j < K; ++j) {
+      const float z = ldT<DT>(logits, base + j);
+      rank += (z > zy) || (z == zy && j < y);
+      se.push(expf(z - m), static_cast<uint32_t>(j));
+      if (eps != 0.f) sz.push(z, static_cast<uint32_t>(j));
+    }
+    const float logS = logf(se.fold(static_cast<uint32_t>(K)));
+    const float t = eps != 0.f ? sz.fold(static_cast<uint32_t>(K)) : 0.f;
+    rows[row] = XentRow{xent_loss(m, logS, zy, t, K, eps), m, logS, rank};
+    nll[row] = static_cast<double>((m - zy) + logS);
+  }
+}
+
+int host_xent_fwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
+                  int64_t ignore_index, float eps, void* rows, void* red, const EvalTopk& topk, void* acc) {
+  XentRow* rp = static_cast<XentRow*>(rows);
+  std::vector<double> nll(static_cast<size_t>(B));
+  GS_DISPATCH_FLOAT(dt, DT, host_xent_rows<DT>(logits, labels, B, K, row_stride, ignore_index, eps, rp, nll.data()));
+  int64_t* ap = B > 0 ? static_cast<int64_t*>(acc) : nullptr;
+  int64_t counted = 0, bad = 0;
+  double total = 0.0, total_nll = 0.0;
+  for (int64_t r = 0; r < B; ++r) {  // ascending row order
+    const XentRow w = rp[r];
+    if (w.code >= 0) {
+      total += static_cast<double>(w.loss);
+      total_nll += nll[r];
+      counted += 1;
+      if (ap)
+        for (int i = 0; i < topk.n; ++i) ap[4 + i] += w.code < topk.k[i];
+    } else if (w.code == kEvalBad) {
+      bad += 1;
+    }
+  }
+  *static_cast<XentRed*>(red) = xent_reduce(total, counted, bad);
+  if (ap) {
+    ap[0] += counted;
+    ap[1] += bad;
+    double cur;
+    std::memcpy(&cur, ap + 2, 8);
+    cur = cur + total_nll;
+    std::memcpy(ap + 2, &cur, 8);
+  }
+  return GS_OK;
+}
+
+template <int DT>
+void host_xent_grad(const void* logits, const int64_t* labels, int64_t B, int K, int64_t row_stride, float eps,
+                    int reduction, const XentRow* rows, const XentRed* red, const float* grad_out, void* dlogits,
+                    int64_t d_row_stride) {
+  const float q_off = eps / static_cast<float>(K);
+  const float q_on = (1.f - eps) + q_off;
+  for (int64_t row = 0; row < B; ++row) {
+    const XentRow w = rows[row];
+    const int64_t zb = row * row_stride, db = row * d_row_stride;
+    if (w.code < 0) {
+      for (int j = 0; j < K; ++j) stT<DT>(dlogits, db + j, 0.f);
+      continue;
+    }
+    const int64_t y = labels[row];
+    const float g = grad_out[reduction == kXentNone ? row : 0];
+    const float c = reduction == kXentMean ? g / static_cast<float>(red->counted) : g;
+    for (int j = 0; j < K; ++j)
+      stT<DT>(dlogits, db + j, xent_grad(ldT<DT>(logits, zb + j), w.m, w.logS, j == y ? q_on : q_off, c));
+  }
+}
+
+int host_xent_bwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride, float eps,
+                  int reduction, const void* rows, const void* red, const float* grad_out, void* dlogits,
+                  int64_t d_row_stride) {
+  GS_DISPATCH_FLOAT(dt, DT, host_xent_grad<DT>(logits, labels, B, K, row_stride, eps, reduction,
+                                               static_cast<const XentRow*>(rows), static_cast<const XentRed*>(red),
+                                               grad_out, dlogits, d_row_stride));
   return GS_OK;
 }
 

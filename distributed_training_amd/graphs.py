@@ -31,7 +31,8 @@ What stays correct across replays:
 
 Requirements are torch.cuda.graph's: static shapes (the same batch size on
 every call — a ragged last batch runs eagerly), no host synchronisation inside
-the step (``loss.item()`` belongs outside), and a ``zero_grad`` inside the
+the step (``loss.item()`` belongs outside; ``loss.CrossEntropyLoss(metrics=...)``
+keeps a running loss on the device instead), and a ``zero_grad`` inside the
 step so that recorded grads are reused: `zero_grad(set_to_none=True)` at the
 start of the step is the cheap form (the recorded backward then writes fresh
 grads in the graph pool; `set_to_none=False` records a fill + an accumulate

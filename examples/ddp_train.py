@@ -13,6 +13,10 @@ same shape is used.
 
 ``--eval`` evaluates on the test set after every epoch (``distributed_training_amd.evaluate``: every test
 sample counted once across the ranks) and prints one line on rank 0.
+
+``--fused-loss`` swaps ``nn.CrossEntropyLoss`` for ``distributed_training_amd.CrossEntropyLoss`` with a
+``Metrics``: the loop then never reads the loss from the device, and the epoch's mean (unsmoothed) loss and
+top-1 over all ranks come from one ``compute()`` at its end.  ``--label-smoothing`` goes to either criterion.
 """
 from __future__ import annotations
 
@@ -27,7 +31,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from distributed_training_amd import DDP, FusedAdam as Adam, evaluate  # noqa: E402
+from distributed_training_amd import DDP, CrossEntropyLoss, FusedAdam as Adam, Metrics, evaluate  # noqa: E402
 from distributed_training_amd import data as D  # noqa: E402
 from distributed_training_amd.resnet import MODELS  # noqa: E402
 
@@ -45,8 +49,13 @@ def build_dataloader(batch_size: int, device, synthetic_n: int = 50000):
 
 
 def train_epoch(epoch, num_epochs, model, optimizer, criterion, train_dataloader, max_steps=None):
-    """R:ddp_train.py:52-75 (tqdm progress bar omitted); returns the last loss."""
+    """R:ddp_train.py:52-75 (tqdm progress bar omitted); returns the last loss, or, for a criterion that
+    carries a ``Metrics``, the epoch's ``compute()`` summed over the ranks (the only host read)."""
     model.train()
+    metrics = getattr(criterion, "metrics", None)
+    if metrics is not None:
+        criterion.train()
+        metrics.reset()
     loss = None
     for k, (images, labels) in enumerate(train_dataloader):
         if max_steps is not None and k >= max_steps:
@@ -56,11 +65,15 @@ def train_epoch(epoch, num_epochs, model, optimizer, criterion, train_dataloader
         loss.backward()
         optimizer.step()
         optimizer.zero_grad()
+    if metrics is not None:
+        metrics.reduce()
+        return metrics.compute()
     return None if loss is None else loss.item()
 
 
 def ddp(rank, world_size, num_epochs, learning_rate, batch_size, device_type="cuda", max_steps=None,
-        synthetic_n=50000, port=12355, result=None, local_rank=None, run_eval=False):
+        synthetic_n=50000, port=12355, result=None, local_rank=None, run_eval=False, label_smoothing=0.0,
+        fused_loss=False):
     """R:ddp_train.py:94-105 (ddp_setup :79-85 with the backend chosen by device).  ``run_eval``: after each
     epoch, evaluate on the test loader the reference builds and never drains (:47)."""
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -76,12 +89,20 @@ def ddp(rank, world_size, num_epochs, learning_rate, batch_size, device_type="cu
     model = DDP(MODELS["resnet18"](num_classes=10).to(device))
     train_dataloader, test_dataloader = build_dataloader(batch_size, device, synthetic_n)
     optimizer = Adam(model.parameters(), lr=learning_rate)
-    criterion = nn.CrossEntropyLoss()
+    if fused_loss:
+        criterion = CrossEntropyLoss(label_smoothing=label_smoothing, metrics=Metrics(topk=(1,), device=device))
+    elif label_smoothing:
+        criterion = nn.CrossEntropyLoss(label_smoothing=label_smoothing)
+    else:
+        criterion = nn.CrossEntropyLoss()
     last = None
     for epoch in range(num_epochs):
         train_dataloader.sampler.set_epoch(epoch)
         last = train_epoch(epoch, num_epochs, model, optimizer, criterion, train_dataloader, max_steps)
-        if rank == 0:
+        if rank == 0 and fused_loss:
+            print(f"epoch {epoch + 1}/{num_epochs} n {last['n']} mean loss {last['loss']:.4f} "
+                  f"top1 {last['top1']:.4f}", flush=True)
+        elif rank == 0:
             print(f"epoch {epoch + 1}/{num_epochs} loss {last:.4f}", flush=True)
         if run_eval:
             m = evaluate(model, test_dataloader, max_batches=max_steps)
@@ -102,15 +123,19 @@ def main():
     ap.add_argument("--batch-size", type=int, default=100)
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--eval", action="store_true", help="evaluate on the test set after each epoch")
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="the fused criterion with device-side running metrics instead of nn.CrossEntropyLoss")
     a = ap.parse_args()
     if "RANK" in os.environ:  # torchrun
         ws = int(os.environ["WORLD_SIZE"])
         ddp(int(os.environ["RANK"]), ws, a.epochs, 1e-3 * ws, a.batch_size, a.device, a.max_steps,
-            local_rank=int(os.environ.get("LOCAL_RANK", "0")), run_eval=a.eval)
+            local_rank=int(os.environ.get("LOCAL_RANK", "0")), run_eval=a.eval, label_smoothing=a.label_smoothing,
+            fused_loss=a.fused_loss)
     else:
         ws = a.world_size
         mp.spawn(ddp, args=(ws, a.epochs, 1e-3 * ws, a.batch_size, a.device, a.max_steps, 50000, 12355, None, None,
-                            a.eval), nprocs=ws)
+                            a.eval, a.label_smoothing, a.fused_loss), nprocs=ws)
 
 
 if __name__ == "__main__":

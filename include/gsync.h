@@ -849,6 +849,71 @@ int gs_eval_accumulate(int device_kind, const void* logits, int logits_dtype, co
                        int64_t K, int64_t row_stride, int64_t n_valid, const int32_t* topk, int n_topk,
                        int64_t ignore_index, void* ws, void* acc, void* stream);
 
+/* ======================================================================
+ * Training criterion: cross-entropy with label smoothing, forward and backward
+ * (csrc/gs_loss_kernels.hip; Python: distributed_training_amd/loss.py)
+ * replaces: of a training step under autocast, the cast of the logits to fp32 +
+ *           log_softmax + nll_loss (+ a row sum and elementwise ops with label
+ *           smoothing), their backwards and the cast back, and the per-step
+ *           loss.item() a running loss needs
+ * ==================================================================== */
+/* The loss of one batch.  logits, labels, row_stride, ignore_index: as gs_eval_accumulate.
+ * label_smoothing = eps in [0, 1].  rows: output, 16 bytes per row:
+ *   {fp32 loss, fp32 m, fp32 logS, int32 code}
+ * code follows gs_eval_accumulate's rules: the label's rank >= 0 (ties to the lower index),
+ * INT32_MAX for a row that holds a NaN, -1 for a row whose label is ignore_index, -2 for a
+ * label outside [0, K).  red: output, 16 bytes:
+ *   {fp32 loss_sum, fp32 loss_mean, int32 counted, int32 bad}
+ * A counted row (code >= 0), with z the row converted to fp32 and y its label:
+ *   m = max z;  S = sum_j expf(z_j - m) (gs_eval_accumulate's balanced tree: at most
+ *   ceil(log2 K) roundings on a path);  logS = logf(S);  nll = (m - z_y) + logS
+ *   eps > 0:  T = sum_j z_j on the same tree;  smooth = (m + logS) - T / (float)K
+ *             loss = (1 - eps) * nll + eps * smooth
+ *   eps == 0: loss = nll; the smoothing term is not formed, so a -inf logit on a masked
+ *             class leaves the loss finite
+ * every multiply and add rounded once, no fma.  A row that holds a NaN has loss, m and logS
+ * NaN.  A row that is not counted gets {0, 0, 0, code}.  A label outside [0, K) that is not
+ * ignore_index is tallied in red.bad (and acc[1]) and makes loss_sum and loss_mean NaN:
+ * that is the visible signal; there is no device assert and no host read.
+ * The counted rows' losses are added in ascending row order in fp64 and rounded once:
+ * loss_sum = (float)total, loss_mean = (float)(total / counted); counted == 0 gives
+ * sum 0 and mean NaN.
+ * acc (nullable) with topk / n_topk: an accumulator with gs_eval_accumulate's layout; it is
+ * advanced by this batch's counted and bad rows, its top-k hits and the sum of the UNSMOOTHED
+ * losses nll (ascending row order, fp64), as gs_eval_accumulate with n_valid = B would.
+ * rows, red, acc live where device_kind says.  Bitwise repeatable: no floating-point atomics.
+ * GS_DEV_HIP: two launches on `stream` (one wavefront per row, then one workgroup that
+ * folds), no allocation, no host synchronisation, capturable.  GS_DEV_HOST: the same rules;
+ * the trees have the same depth but another order and expf / logf are the host's, so a loss
+ * may differ from the device's by a few fp32 ulps while every code and count is the same.
+ * GS_EINVAL before any launch: an unknown device kind or dtype, B < 0, K outside [1, 2^30],
+ * row_stride < K, eps outside [0, 1] or NaN, n_topk outside [0, 4], a k < 1, a null or
+ * misaligned pointer (rows and red 16 bytes, acc 8 bytes).  B == 0 writes
+ * red = {0, NaN, 0, 0} and touches nothing else. */
+int gs_xent_fwd(int device_kind, const void* logits, int logits_dtype, const int64_t* labels, int64_t B, int64_t K,
+                int64_t row_stride, int64_t ignore_index, float label_smoothing, void* rows, void* red,
+                const int32_t* topk, int n_topk, void* acc, void* stream);
+/* The gradient of that loss with respect to the logits.  logits, labels, label_smoothing:
+ * what the forward saw; rows, red: what it wrote.  reduction: 0 none, 1 mean, 2 sum.
+ * grad_out: fp32 where device_kind says, one element for mean and sum, [B] for none; it is
+ * read by the kernel, never on the host.  dlogits: [B, K] in the logits' dtype, row r at
+ * dlogits + r * d_row_stride elements; it does not overlap logits.  A counted row:
+ *   c = g / (float)counted (mean), g (sum), g[r] (none)
+ *   q_off = eps / (float)K;  q_on = (1 - eps) + q_off;  q_j = q_on if j == y else q_off
+ *   p_j = expf((z_j - m) - logS);  dz_j = c * (p_j - q_j)
+ * each step rounded once, no fma, then dz_j rounded once to the logits' dtype.  A row that is
+ * not counted (code < 0) gets K zeros; a NaN row gets K NaNs.  Elements K ... row_stride - 1
+ * of a row are never read as data and never written.
+ * GS_DEV_HIP: one launch on `stream`; a wavefront takes 2048 consecutive elements of a row,
+ * so a row of K <= 2048 is one wavefront's and a longer one several.  Loads and stores are
+ * 16 bytes wide when logits, dlogits and both row strides in bytes are multiples of 16, and
+ * one element wide otherwise.  Repeatable, capturable, no allocation.
+ * GS_EINVAL before the launch: as gs_xent_fwd, an unknown reduction, d_row_stride < K,
+ * dlogits overlapping logits.  B == 0 is a no-op. */
+int gs_xent_bwd(int device_kind, const void* logits, int logits_dtype, const int64_t* labels, int64_t B, int64_t K,
+                int64_t row_stride, int64_t ignore_index, float label_smoothing, int reduction, const void* rows,
+                const void* red, const float* grad_out, void* dlogits, int64_t d_row_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
