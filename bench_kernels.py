@@ -295,6 +295,99 @@ def main():
             rec("xent_step", 3 * Bx * Kx * zx.element_size(), *f_ms, "libgsync", B=Bx, K=Kx, dtype=str(dt)[6:],
                 label_smoothing=0.1, launches=f_n, torch_median_ms=t_ms[0], torch_avg_ms=t_ms[1],
                 torch_batched_avg_ms=t_batched, torch_launches=t_n, ratio_to_torch=f_ms[0] / t_ms[0])
+    # the pair-target criterion (gs_xent_mix_fwd + gs_xent_mix_bwd through loss.cross_entropy with a MixedTarget)
+    # beside the one-label criterion and the torch two-call composition on the same logits, all from this run
+    if want("xent_mix"):
+        import torch.nn.functional as F
+
+        from distributed_training_amd.data import MixedTarget
+        from distributed_training_amd.loss import cross_entropy
+
+        Bx, Kx, dt = 256, 1000, torch.bfloat16
+        zx = (torch.randn(Bx, Kx, device=dev, generator=g) * 3).to(dt).requires_grad_()
+        tx = MixedTarget(torch.randint(0, Kx, (Bx,), device=dev, generator=g),
+                         torch.randint(0, Kx, (Bx,), device=dev, generator=g),
+                         torch.rand(Bx, device=dev, generator=g))
+
+        def mix_step():
+            zx.grad = None
+            cross_entropy(zx, tx, label_smoothing=0.1).backward()
+
+        def one_step():
+            zx.grad = None
+            cross_entropy(zx, tx.labels_a, label_smoothing=0.1).backward()
+
+        def torch_mix_step():
+            zx.grad = None
+            z32 = zx.float()
+            (tx.lam * F.cross_entropy(z32, tx.labels_a, reduction="none", label_smoothing=0.1)
+             + (1 - tx.lam) * F.cross_entropy(z32, tx.labels_b, reduction="none", label_smoothing=0.1)).mean().backward()
+
+        o_ms, t_ms = timeit(one_step, args.iters), timeit(torch_mix_step, args.iters)
+        t_batched = timeit_batched(torch_mix_step, args.iters)
+        o_batched = timeit_batched(one_step, args.iters)
+        f_ms = timeit(mix_step, args.iters)
+        rec("xent_mix_step", 3 * Bx * Kx * zx.element_size(), *f_ms, "libgsync", B=Bx, K=Kx, dtype=str(dt)[6:],
+            label_smoothing=0.1, xent_median_ms=o_ms[0], xent_avg_ms=o_ms[1], xent_batched_avg_ms=o_batched,
+            torch_median_ms=t_ms[0], torch_avg_ms=t_ms[1], torch_batched_avg_ms=t_batched,
+            ratio_to_torch=f_ms[0] / t_ms[0], ratio_to_xent=f_ms[0] / o_ms[0])
+    # the mixed input step (gs_image_augment_mix) at CIFAR geometry, half the records blends and half pastes,
+    # beside the unmixed gs_image_augment and gs_image_augment followed by the torch composition of the same mix
+    # (a gather, two multiplies, an add, a masked select), all from this run
+    if want("augment_mix"):
+        import numpy as np
+
+        from distributed_training_amd import data as D
+
+        ds = D.ImageDataset.synthetic(50000, device=dev, seed=0)
+        for Ba in (256, 4096):
+            rng = np.random.default_rng(Ba)
+            prm = np.stack([rng.integers(0, ds.n, Ba), rng.integers(0, 2, Ba), rng.integers(0, 9, Ba),
+                            rng.integers(0, 9, Ba)], axis=1).astype(np.int32)
+            recs = np.zeros((Ba, 4), dtype=np.int32)
+            recs[:, 0] = rng.permutation(Ba)
+            lam_np = rng.random(Ba, dtype=np.float32)
+            paste = np.arange(Ba) % 2 == 1
+            lam_np[paste] = np.float32(1.0 - 16 * 16 / 1024.0)
+            recs[:, 1] = lam_np.view(np.int32)
+            recs[paste, 2] = 8 | (24 << 16)
+            recs[paste, 3] = 8 | (24 << 16)
+            dprm, drec = torch.from_numpy(prm).to(dev), torch.from_numpy(recs).to(dev)
+            xa = torch.empty(Ba, 3, 32, 32, device=dev)
+            la, lb_ = torch.empty(Ba, dtype=torch.int64, device=dev), torch.empty(Ba, dtype=torch.int64, device=dev)
+            lm = torch.empty(Ba, device=dev)
+            perm = torch.from_numpy(recs[:, 0].astype(np.int64)).to(dev)
+            lam_t = torch.from_numpy(lam_np).to(dev).view(Ba, 1, 1, 1)
+            box = torch.zeros(Ba, 1, 32, 32, dtype=torch.bool, device=dev)
+            box[torch.from_numpy(paste).to(dev), :, 8:24, 8:24] = True
+            blend = torch.from_numpy(~paste).to(dev).view(Ba, 1, 1, 1)
+            st = torch.cuda.current_stream().cuda_stream
+
+            def plain():
+                L.check(L.lib().gs_image_augment(L.GS_DEV_HIP, 0, ds.images.data_ptr(), ds.labels.data_ptr(), ds.n, 32,
+                                                 32, 3, 4, 32, 32, dprm.data_ptr(), Ba, xa.data_ptr(), L.GS_F32,
+                                                 L.GS_LAYOUT_NCHW, la.data_ptr(), st))
+
+            def fused():
+                L.check(L.lib().gs_image_augment_mix(L.GS_DEV_HIP, 0, ds.images.data_ptr(), ds.labels.data_ptr(), ds.n,
+                                                     32, 32, 3, 4, 32, 32, dprm.data_ptr(), drec.data_ptr(), Ba,
+                                                     xa.data_ptr(), L.GS_F32, L.GS_LAYOUT_NCHW, la.data_ptr(),
+                                                     lb_.data_ptr(), lm.data_ptr(), st))
+
+            def composed():
+                plain()
+                xb = xa[perm]
+                return torch.where(box, xb, torch.where(blend, xa * lam_t + xb * (1 - lam_t), xa)), la[perm]
+
+            p_ms, c_ms = timeit(plain, args.iters), timeit(composed, args.iters)
+            p_batched, c_batched = timeit_batched(plain, args.iters), timeit_batched(composed, args.iters)
+            f_ms = timeit(fused, args.iters)
+            rec("augment_mix", Ba * (2 * 3072 + 4 * 3072), *f_ms, "libgsync", B=Ba, geometry="32x32x3 pad 4 crop 32",
+                out="f32 nchw", augment_median_ms=p_ms[0], augment_avg_ms=p_ms[1], augment_batched_avg_ms=p_batched,
+                augment_plus_torch_median_ms=c_ms[0], augment_plus_torch_avg_ms=c_ms[1],
+                augment_plus_torch_batched_avg_ms=c_batched, ratio_to_augment=f_ms[0] / p_ms[0],
+                ratio_to_augment_plus_torch=f_ms[0] / c_ms[0])
+        del ds
     if not args.skip_torch and want("lamb"):
         # a LAMB step of the same arithmetic as torch foreach ops, everything on the device
         bp, bm, bv = [p.clone() for p in params], [x.clone() for x in ms], [x.clone() for x in vs]

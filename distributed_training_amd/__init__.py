@@ -12,6 +12,8 @@ Public surface:
                             sample counted once, the fused inference BatchNorm forward
   CrossEntropyLoss / cross_entropy  the fused training criterion (label smoothing, fp32 loss, gradient
                             in the logits' dtype), optionally advancing a Metrics on the device
+  MixUpCutMix / MixedTarget  MixUp and CutMix inside the device input kernel (data.DeviceDataLoader(mix=...))
+                            and the pair targets the criterion takes in place of labels
   compat.deepspeed / compat.colossalai  API shims for the other two trainers
 """
 from . import _lib  # noqa: F401
@@ -19,6 +21,7 @@ from .comm import Communicator, destroy_communicators, get_communicator  # noqa:
 from .ddp import DDP, DistributedDataParallel, GradBucket, compute_bucket_assignment_by_size  # noqa: F401
 from .graphs import CapturedStep  # noqa: F401
 from .ema import AveragedModel, ShardedAveragedModel, get_ema_multi_avg_fn, get_swa_multi_avg_fn  # noqa: F401
+from .data import MixedTarget, MixUpCutMix  # noqa: F401
 from .evaluation import Metrics, evaluate  # noqa: F401
 from .loss import CrossEntropyLoss, cross_entropy  # noqa: F401
 from .flatten import copy_flat_to, flatten_dense_tensors, unflatten_dense_tensors  # noqa: F401

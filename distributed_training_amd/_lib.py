@@ -120,6 +120,8 @@ SIGNATURES = {
                                      _vp]),
     "gs_image_augment": (_c_int, [_c_int, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                   _vp, _c_i64, _vp, _c_int, _c_int, _vp, _vp]),
+    "gs_image_augment_mix": (_c_int, [_c_int, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                      _vp, _vp, _c_i64, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp]),
     "gs_bn_bwd_partials": (_c_int, [_c_i64, _c_int]),
     "gs_bn_bwd_reduce": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _vp]),
     "gs_bn_bwd_reduce_fork": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _vp]),
@@ -141,6 +143,10 @@ SIGNATURES = {
                              _vp, _vp]),
     "gs_xent_bwd": (_c_int, [_c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f, _c_int, _vp, _vp, _vp, _vp,
                              _c_i64, _vp]),
+    "gs_xent_mix_fwd": (_c_int, [_c_int, _vp, _c_int, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f, _vp, _vp,
+                                 _p_i32, _c_int, _vp, _vp]),
+    "gs_xent_mix_bwd": (_c_int, [_c_int, _vp, _c_int, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f, _c_int, _vp,
+                                 _vp, _vp, _vp, _c_i64, _vp]),
     "gs_clip_coef":(_c_int, [_c_int, _vp, _c_f, _c_f, _vp, _vp, _vp]),
     "gs_unscale_check": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),
     "gs_sgd_step": (

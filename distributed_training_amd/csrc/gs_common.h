@@ -225,6 +225,51 @@ GS_HD inline float aug_pixel(const uint8_t* src, int64_t idx, int H, int W, int 
 }
 int hip_image_augment(int device, const ImageAugArgs& a, void* stream);
 
+// gs_image_augment_mix: the batch of ImageAugArgs with a MixUp / CutMix record per sample.
+struct ImageMixAugArgs : ImageAugArgs {
+  const int32_t* mix;      // [B, 4] = (partner, lam as fp32 bits, y0 | y1 << 16, x0 | x1 << 16)
+  int64_t* out_labels_b;   // [B] or NULL
+  float* out_lam;          // [B] or NULL
+};
+// A sample's record as both backends read it.  The host backend has rejected what is invalid;
+// the device cannot, so here a partner outside [0, B) or a lam outside [0, 1] (or NaN) makes
+// the sample its own partner with lam 1, and a box is clamped to the output extent.
+struct MixRec {
+  int partner;
+  float lam;
+  int y0, y1, x0, x1;
+  bool box;     // a non-empty box: paste the partner inside it
+  bool need_b;  // the partner's image is read
+};
+GS_HD inline MixRec mix_decode(int32_t w0, int32_t w1, int32_t w2, int32_t w3, int64_t i, int64_t B, int out_h,
+                               int out_w) {
+  MixRec r;
+  uint32_t lb = static_cast<uint32_t>(w1);
+  float lam;
+  __builtin_memcpy(&lam, &lb, 4);
+  const bool ok = w0 >= 0 && w0 < B && lam >= 0.f && lam <= 1.f;
+  r.partner = ok ? w0 : static_cast<int>(i);
+  r.lam = ok ? lam : 1.f;
+  const uint32_t ys = static_cast<uint32_t>(w2), xs = static_cast<uint32_t>(w3);
+  const int y0 = static_cast<int>(ys & 0xffffu), y1 = static_cast<int>(ys >> 16);
+  const int x0 = static_cast<int>(xs & 0xffffu), x1 = static_cast<int>(xs >> 16);
+  r.y0 = y0 < out_h ? y0 : out_h;
+  r.y1 = y1 < out_h ? y1 : out_h;
+  r.x0 = x0 < out_w ? x0 : out_w;
+  r.x1 = x1 < out_w ? x1 : out_w;
+  r.box = ok && r.y0 < r.y1 && r.x0 < r.x1;
+  r.need_b = r.partner != i && (r.box || r.lam != 1.f);
+  return r;
+}
+// One output element from the sample's pixel a and the partner's pixel b (need_b holds):
+// paste inside a box, else the blend, each multiply and the add rounded once.
+GS_HD inline float mix_pixel(float a, float b, const MixRec& r, int y, int x) {
+  if (r.box) return (y >= r.y0 && y < r.y1 && x >= r.x0 && x < r.x1) ? b : a;
+  const float lam1 = 1.f - r.lam;
+  return a * r.lam + b * lam1;
+}
+int hip_image_augment_mix(int device, const ImageMixAugArgs& a, void* stream);
+
 // Adam's step-varying hyper-parameters from a device step counter (torch's
 // capturable=True): step += 1 unless found_inf; then, in double as the host
 // path forms them, hyper = [-(lr/bc1), sqrt(bc2), 1 - lr*wd] rounded to fp32.
@@ -333,17 +378,44 @@ GS_HD inline float xent_grad(float z, float m, float logS, float q, float c) {
   const float p = expf((z - m) - logS);
   return c * (p - q);
 }
+// ---- pair targets (gs_xent_mix_fwd / gs_xent_mix_bwd): labels a and b and a's weight lam ----
+// the code of a row that is not counted, or 0: skipped if either label is ignore_index, else bad
+// if either is outside [0, K) or lam is outside [0, 1] or NaN
+GS_HD inline int32_t xent_mix_code(int64_t a, int64_t b, float lam, int K, int64_t ignore_index) {
+  if (a == ignore_index || b == ignore_index) return kEvalSkip;
+  if (a < 0 || a >= K || b < 0 || b >= K || !(lam >= 0.f && lam <= 1.f)) return kEvalBad;
+  return 0;
+}
+// a one-label row: exactly the one-label entries' row for label a
+GS_HD inline bool xent_mix_one(int64_t a, int64_t b, float lam) { return lam == 1.f || a == b; }
+// the label Metrics count top-k against
+GS_HD inline int64_t xent_mix_dominant(int64_t a, int64_t b, float lam) { return lam >= 0.5f ? a : b; }
+// a mixed row's loss from its two one-label losses
+GS_HD inline float xent_mix_loss(float m, float logS, float za, float zb, float lam, float T, int K, float eps) {
+  const float lam1 = 1.f - lam;
+  return lam * xent_loss(m, logS, za, T, K, eps) + lam1 * xent_loss(m, logS, zb, T, K, eps);
+}
+// a mixed row's target at one of its two labels, w = lam or 1 - lam
+GS_HD inline float xent_mix_q(float eps, float w, float q_off) { return (1.f - eps) * w + q_off; }
 int hip_xent_fwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
                  int64_t ignore_index, float eps, void* rows, void* red, const EvalTopk& topk, void* acc,
                  void* stream);
-int host_xent_fwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
-                  int64_t ignore_index, float eps, void* rows, void* red, const EvalTopk& topk, void* acc);
 int hip_xent_bwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride, float eps,
                  int reduction, const void* rows, const void* red, const float* grad_out, void* dlogits,
                  int64_t d_row_stride, void* stream);
-int host_xent_bwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride, float eps,
-                  int reduction, const void* rows, const void* red, const float* grad_out, void* dlogits,
-                  int64_t d_row_stride);
+// pair targets; the host functions serve the one-label entries too (labels_b and lam null)
+int hip_xent_mix_fwd(const void* logits, int dt, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                     int64_t B, int K, int64_t row_stride, int64_t ignore_index, float eps, void* rows, void* red,
+                     const EvalTopk& topk, void* acc, void* stream);
+int host_xent_mix_fwd(const void* logits, int dt, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      int64_t B, int K, int64_t row_stride, int64_t ignore_index, float eps, void* rows, void* red,
+                      const EvalTopk& topk, void* acc);
+int hip_xent_mix_bwd(const void* logits, int dt, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                     int64_t B, int K, int64_t row_stride, float eps, int reduction, const void* rows, const void* red,
+                     const float* grad_out, void* dlogits, int64_t d_row_stride, void* stream);
+int host_xent_mix_bwd(const void* logits, int dt, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      int64_t B, int K, int64_t row_stride, float eps, int reduction, const void* rows,
+                      const void* red, const float* grad_out, void* dlogits, int64_t d_row_stride);
 
 // Deferred watchdog marks (gs_comm.cpp): a consumer plan's launch carries the mark of
 // the collectives deferred to it.  comm_mark_take: 0 = nothing to do (the

@@ -26,6 +26,7 @@
 // u64 next | u64 state[624] | normal-sample caches), so the loader consumes
 // the global generator exactly as the reference's DataLoader does.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
 #include "gs_common.h"
@@ -97,12 +98,22 @@ void store_torch_state(const Mt19937& m, uint8_t* st) {
   }
 }
 
-int host_image_augment(const ImageAugArgs& a) {
+// mx == nullptr: gs_image_augment; else gs_image_augment_mix's records on top of the same pixels
+int host_image_augment(const ImageAugArgs& a, const ImageMixAugArgs* mx = nullptr) {
   const int64_t per = static_cast<int64_t>(a.C) * a.out_h * a.out_w;
   for (int64_t b = 0; b < a.B; ++b) {
     const int32_t* pr = a.params + 4 * b;
     const int64_t idx = pr[0];
     if (a.out_labels) a.out_labels[b] = a.labels ? a.labels[idx] : 0;
+    MixRec r{};
+    const int32_t* pp = pr;
+    if (mx) {
+      const int32_t* m = mx->mix + 4 * b;
+      r = mix_decode(m[0], m[1], m[2], m[3], b, a.B, a.out_h, a.out_w);
+      pp = a.params + 4 * static_cast<int64_t>(r.partner);
+      if (mx->out_labels_b) mx->out_labels_b[b] = a.labels ? a.labels[pp[0]] : 0;
+      if (mx->out_lam) mx->out_lam[b] = r.lam;
+    }
     for (int64_t k = 0; k < per; ++k) {
       int c, y, x;
       if (a.layout == GS_LAYOUT_NCHW) {
@@ -114,7 +125,9 @@ int host_image_augment(const ImageAugArgs& a) {
         x = static_cast<int>((k / a.C) % a.out_w);
         y = static_cast<int>(k / (static_cast<int64_t>(a.C) * a.out_w));
       }
-      const float v = aug_pixel(a.src, idx, a.H, a.W, a.C, a.pad, pr[1], pr[2], pr[3], c, y, x);
+      float v = aug_pixel(a.src, idx, a.H, a.W, a.C, a.pad, pr[1], pr[2], pr[3], c, y, x);
+      if (r.need_b)
+        v = mix_pixel(v, aug_pixel(a.src, pp[0], a.H, a.W, a.C, a.pad, pp[1], pp[2], pp[3], c, y, x), r, y, x);
       const int64_t o = b * per + k;
       if (a.out_dtype == GS_F32) static_cast<float*>(a.out)[o] = v;
       else static_cast<uint16_t*>(a.out)[o] = f32_to_bf16(v);
@@ -214,31 +227,85 @@ int gs_crop_flip_params(const int64_t* indices, int64_t B, int in_h, int in_w, i
   return GS_OK;
 }
 
-int gs_image_augment(int device_kind, int device, const uint8_t* src, const int64_t* labels, int64_t n_src,
-                     int H, int W, int C, int pad, int out_h, int out_w, const int32_t* params, int64_t B,
-                     void* out, int out_dtype, int out_layout, int64_t* out_labels, void* stream) {
-  GS_CHECK_ARG(device_kind == GS_DEV_HOST || device_kind == GS_DEV_HIP, "gs_image_augment: bad device_kind");
+// the checks gs_image_augment and gs_image_augment_mix share; *done: an empty batch
+static int augment_check(const std::string& w, int device_kind, const uint8_t* src, int64_t n_src, int H, int W,
+                         int C, int pad, int out_h, int out_w, const int32_t* params, int64_t B, const void* out,
+                         int out_dtype, int out_layout, bool* done) {
+  *done = false;
+  GS_CHECK_ARG(device_kind == GS_DEV_HOST || device_kind == GS_DEV_HIP, w + ": bad device_kind");
   GS_CHECK_ARG(B >= 0 && n_src >= 0 && H > 0 && W > 0 && C > 0 && pad >= 0 && out_h > 0 && out_w > 0,
-               "gs_image_augment: bad geometry");
-  GS_CHECK_ARG(out_h <= H + 2 * pad && out_w <= W + 2 * pad, "gs_image_augment: crop larger than padded image");
-  GS_CHECK_ARG(out_dtype == GS_F32 || out_dtype == GS_BF16, "gs_image_augment: out dtype must be f32 or bf16");
-  GS_CHECK_ARG(out_layout == GS_LAYOUT_NCHW || out_layout == GS_LAYOUT_NHWC, "gs_image_augment: bad layout");
-  if (B == 0) return GS_OK;
-  GS_CHECK_ARG(src && params && out, "gs_image_augment: NULL buffer");
-  ImageAugArgs a{src, labels, n_src, H, W, C, pad, out_h, out_w, params, B, out, out_dtype, out_layout, out_labels};
+               w + ": bad geometry");
+  GS_CHECK_ARG(out_h <= H + 2 * pad && out_w <= W + 2 * pad, w + ": crop larger than padded image");
+  GS_CHECK_ARG(out_dtype == GS_F32 || out_dtype == GS_BF16, w + ": out dtype must be f32 or bf16");
+  GS_CHECK_ARG(out_layout == GS_LAYOUT_NCHW || out_layout == GS_LAYOUT_NHWC, w + ": bad layout");
+  if (B == 0) {
+    *done = true;
+    return GS_OK;
+  }
+  GS_CHECK_ARG(src && params && out, w + ": NULL buffer");
   if (device_kind == GS_DEV_HOST) {
     // host params are readable: bounds-check every sample (the device path
     // trusts the caller, which validated the same params before the upload)
     for (int64_t b = 0; b < B; ++b) {
       const int32_t* p = params + 4 * b;
-      GS_CHECK_ARG(p[0] >= 0 && p[0] < n_src, "gs_image_augment: sample index out of range");
+      GS_CHECK_ARG(p[0] >= 0 && p[0] < n_src, w + ": sample index out of range");
       GS_CHECK_ARG(p[2] >= 0 && p[2] + out_h <= H + 2 * pad && p[3] >= 0 && p[3] + out_w <= W + 2 * pad,
-                   "gs_image_augment: crop offset out of range");
+                   w + ": crop offset out of range");
     }
-    return host_image_augment(a);
   }
-  if (hip_device_count() <= device) return fail(GS_ENODEV, "gs_image_augment: HIP device not available");
+  return GS_OK;
+}
+
+int gs_image_augment(int device_kind, int device, const uint8_t* src, const int64_t* labels, int64_t n_src,
+                     int H, int W, int C, int pad, int out_h, int out_w, const int32_t* params, int64_t B,
+                     void* out, int out_dtype, int out_layout, int64_t* out_labels, void* stream) {
+  const std::string w("gs_image_augment");
+  bool done;
+  GS_TRY_RET(augment_check(w, device_kind, src, n_src, H, W, C, pad, out_h, out_w, params, B, out, out_dtype,
+                           out_layout, &done));
+  if (done) return GS_OK;
+  ImageAugArgs a{src, labels, n_src, H, W, C, pad, out_h, out_w, params, B, out, out_dtype, out_layout, out_labels};
+  if (device_kind == GS_DEV_HOST) return host_image_augment(a);
+  if (hip_device_count() <= device) return fail(GS_ENODEV, w + ": HIP device not available");
   return hip_image_augment(device, a, stream);
+}
+
+int gs_image_augment_mix(int device_kind, int device, const uint8_t* src, const int64_t* labels, int64_t n_src,
+                         int H, int W, int C, int pad, int out_h, int out_w, const int32_t* params,
+                         const int32_t* mix, int64_t B, void* out, int out_dtype, int out_layout,
+                         int64_t* out_labels, int64_t* out_labels_b, float* out_lam, void* stream) {
+  const std::string w("gs_image_augment_mix");
+  bool done;
+  GS_TRY_RET(augment_check(w, device_kind, src, n_src, H, W, C, pad, out_h, out_w, params, B, out, out_dtype,
+                           out_layout, &done));
+  GS_CHECK_ARG(out_h <= 0xffff && out_w <= 0xffff && B <= INT32_MAX,
+               w + ": a box edge or a partner does not fit its field");
+  if (done) return GS_OK;
+  GS_CHECK_ARG(mix != nullptr, w + ": NULL buffer");
+  GS_CHECK_ARG(device_kind == GS_DEV_HOST || (reinterpret_cast<uintptr_t>(mix) & 15u) == 0,
+               w + ": mix must be 16-byte aligned");
+  ImageMixAugArgs a{};
+  static_cast<ImageAugArgs&>(a) =
+      ImageAugArgs{src, labels, n_src, H, W, C, pad, out_h, out_w, params, B, out, out_dtype, out_layout, out_labels};
+  a.mix = mix;
+  a.out_labels_b = out_labels_b;
+  a.out_lam = out_lam;
+  if (device_kind == GS_DEV_HOST) {
+    for (int64_t b = 0; b < B; ++b) {
+      const int32_t* m = mix + 4 * b;
+      float lam;
+      std::memcpy(&lam, m + 1, 4);
+      GS_CHECK_ARG(m[0] >= 0 && m[0] < B, w + ": partner out of range");
+      GS_CHECK_ARG(lam >= 0.f && lam <= 1.f, w + ": lam outside [0, 1]");
+      const uint32_t ys = static_cast<uint32_t>(m[2]), xs = static_cast<uint32_t>(m[3]);
+      GS_CHECK_ARG((ys & 0xffffu) <= (ys >> 16) && (ys >> 16) <= static_cast<uint32_t>(out_h) &&
+                       (xs & 0xffffu) <= (xs >> 16) && (xs >> 16) <= static_cast<uint32_t>(out_w),
+                   w + ": box outside the output");
+    }
+    return host_image_augment(a, &a);
+  }
+  if (hip_device_count() <= device) return fail(GS_ENODEV, w + ": HIP device not available");
+  return hip_image_augment_mix(device, a, stream);
 }
 
 }  // extern "C"

@@ -11,10 +11,13 @@
 // with one 16-B (f32) / 8-B (bf16) access; the uint8 reads are byte gathers
 // served from L2 (a sample's 3 KiB image is touched by 12 lanes at most per
 // row).  The per-sample params (index, flip, top, left) arrive as one small
-// device array.
+// device array.  With MIX (gs_image_augment_mix) a second record per sample names
+// a partner in the batch, and the same launch blends or pastes the partner's
+// augmented image into the sample's (MixUp / CutMix).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "gs_common.h"
 
@@ -37,8 +40,18 @@ __device__ __forceinline__ uint16_t to_bf16(float f) {
   return static_cast<uint16_t>((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 
-template <int LAYOUT>
-__device__ __forceinline__ float elem(const ImageAugArgs& a, int64_t e, int64_t per) {
+// the kernels' argument: gs_image_augment's, or with MIX gs_image_augment_mix's (the unmixed
+// instantiations keep their signature)
+template <bool MIX>
+using AugArgs = std::conditional_t<MIX, ImageMixAugArgs, ImageAugArgs>;
+
+__device__ __forceinline__ MixRec mix_record(const ImageMixAugArgs& a, int64_t b) {
+  const int4 m = reinterpret_cast<const int4*>(a.mix)[b];
+  return mix_decode(m.x, m.y, m.z, m.w, b, a.B, a.out_h, a.out_w);
+}
+
+template <int LAYOUT, bool MIX>
+__device__ __forceinline__ float elem(const AugArgs<MIX>& a, int64_t e, int64_t per) {
   const int64_t b = e / per;
   const int64_t k = e - b * per;
   int c, y, x;
@@ -52,12 +65,24 @@ __device__ __forceinline__ float elem(const ImageAugArgs& a, int64_t e, int64_t 
     y = static_cast<int>(k / (static_cast<int64_t>(a.C) * a.out_w));
   }
   const int4 p = reinterpret_cast<const int4*>(a.params)[b];
-  if (p.x < 0 || p.x >= a.n_src) return 0.f;  // never read outside the image set
-  return aug_pixel(a.src, p.x, a.H, a.W, a.C, a.pad, p.y, p.z, p.w, c, y, x);
+  if constexpr (MIX) {
+    const float va =
+        (p.x < 0 || p.x >= a.n_src) ? 0.f : aug_pixel(a.src, p.x, a.H, a.W, a.C, a.pad, p.y, p.z, p.w, c, y, x);
+    const MixRec r = mix_record(a, b);
+    if (!r.need_b) return va;
+    const int4 pb = reinterpret_cast<const int4*>(a.params)[r.partner];
+    const float vb = (pb.x < 0 || pb.x >= a.n_src)
+                         ? 0.f
+                         : aug_pixel(a.src, pb.x, a.H, a.W, a.C, a.pad, pb.y, pb.z, pb.w, c, y, x);
+    return mix_pixel(va, vb, r, y, x);
+  } else {
+    if (p.x < 0 || p.x >= a.n_src) return 0.f;  // never read outside the image set
+    return aug_pixel(a.src, p.x, a.H, a.W, a.C, a.pad, p.y, p.z, p.w, c, y, x);
+  }
 }
 
-template <int LAYOUT, int DT>
-__global__ void __launch_bounds__(256) augment_kernel(ImageAugArgs a, int64_t total, bool vec) {
+template <int LAYOUT, int DT, bool MIX>
+__global__ void __launch_bounds__(256) augment_kernel(AugArgs<MIX> a, int64_t total, bool vec) {
   const int64_t per = static_cast<int64_t>(a.C) * a.out_h * a.out_w;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   const int64_t gid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -65,11 +90,19 @@ __global__ void __launch_bounds__(256) augment_kernel(ImageAugArgs a, int64_t to
     const int idx = reinterpret_cast<const int4*>(a.params)[gid].x;
     a.out_labels[gid] = (a.labels && idx >= 0 && idx < a.n_src) ? a.labels[idx] : 0;
   }
+  if constexpr (MIX) {
+    if (gid < a.B) {
+      const MixRec r = mix_record(a, gid);
+      const int idx = reinterpret_cast<const int4*>(a.params)[r.partner].x;
+      if (a.out_labels_b) a.out_labels_b[gid] = (a.labels && idx >= 0 && idx < a.n_src) ? a.labels[idx] : 0;
+      if (a.out_lam) a.out_lam[gid] = r.lam;
+    }
+  }
   for (int64_t q = gid; q * 4 < total; q += stride) {
     const int64_t e = q * 4;
     float v[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (e + i < total) ? elem<LAYOUT>(a, e + i, per) : 0.f;
+    for (int i = 0; i < 4; ++i) v[i] = (e + i < total) ? elem<LAYOUT, MIX>(a, e + i, per) : 0.f;
     if constexpr (DT == GS_F32) {
       float* o = static_cast<float*>(a.out) + e;
       if (vec && e + 4 <= total) {
@@ -100,10 +133,12 @@ __global__ void __launch_bounds__(256) augment_kernel(ImageAugArgs a, int64_t to
 // 4 consecutive output elements from LDS (32-bit index math only) and writes
 // them with one 16-B / 8-B store.  Used when the image fits the LDS budget
 // (CIFAR: 3 KiB); larger images take augment_kernel (L2-served gathers).
+// MIX: a sample whose record needs its partner stages the partner's image behind its own
+// (a workgroup-uniform branch between the same two barriers), so two images must fit.
 constexpr int kAugLdsBytes = 48 * 1024;
 
-template <int LAYOUT, int DT>
-__global__ void __launch_bounds__(256) augment_lds_kernel(ImageAugArgs a) {
+template <int LAYOUT, int DT, bool MIX>
+__global__ void __launch_bounds__(256) augment_lds_kernel(AugArgs<MIX> a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_img[];
   const int img_bytes = a.H * a.W * a.C;
   const int per = a.C * a.out_h * a.out_w;
@@ -113,11 +148,30 @@ __global__ void __launch_bounds__(256) augment_lds_kernel(ImageAugArgs a) {
     const int4 p = reinterpret_cast<const int4*>(a.params)[b];
     const bool ok = p.x >= 0 && p.x < a.n_src;
     if (threadIdx.x == 0 && a.out_labels) a.out_labels[b] = (ok && a.labels) ? a.labels[p.x] : 0;
+    MixRec r{};
+    int4 pb = p;
+    bool okb = false;
+    if constexpr (MIX) {
+      r = mix_record(a, b);
+      pb = reinterpret_cast<const int4*>(a.params)[r.partner];
+      okb = pb.x >= 0 && pb.x < a.n_src;
+      if (threadIdx.x == 0) {
+        if (a.out_labels_b) a.out_labels_b[b] = (okb && a.labels) ? a.labels[pb.x] : 0;
+        if (a.out_lam) a.out_lam[b] = r.lam;
+      }
+    }
     __syncthreads();  // previous sample's LDS reads are done
     if (ok) {
       const uint8_t* src = a.src + static_cast<int64_t>(p.x) * img_bytes;
       for (int o = threadIdx.x * 16; o < img_bytes; o += 256 * 16)
         *reinterpret_cast<uint4*>(s_img + o) = *reinterpret_cast<const uint4*>(src + o);
+    }
+    if constexpr (MIX) {
+      if (r.need_b && okb) {
+        const uint8_t* src = a.src + static_cast<int64_t>(pb.x) * img_bytes;
+        for (int o = threadIdx.x * 16; o < img_bytes; o += 256 * 16)
+          *reinterpret_cast<uint4*>(s_img + img_bytes + o) = *reinterpret_cast<const uint4*>(src + o);
+      }
     }
     __syncthreads();
     for (int q = threadIdx.x; q < quads; q += 256) {
@@ -143,6 +197,16 @@ __global__ void __launch_bounds__(256) augment_lds_kernel(ImageAugArgs a) {
         v[i] = (ok && sy >= 0 && sy < a.H && sx >= 0 && sx < a.W)
                    ? static_cast<float>(s_img[(sy * a.W + sx) * a.C + c]) / 255.f
                    : 0.f;
+        if constexpr (MIX) {
+          if (r.need_b) {
+            const int qx = pb.y ? (wp - 1 - (x + pb.w)) : (x + pb.w);
+            const int ty = y + pb.z - a.pad, tx = qx - a.pad;
+            const float vb = (okb && ty >= 0 && ty < a.H && tx >= 0 && tx < a.W)
+                                 ? static_cast<float>(s_img[img_bytes + (ty * a.W + tx) * a.C + c]) / 255.f
+                                 : 0.f;
+            v[i] = mix_pixel(v[i], vb, r, y, x);
+          }
+        }
         if constexpr (LAYOUT == GS_LAYOUT_NCHW) {
           if (++x == a.out_w) { x = 0; if (++y == a.out_h) { y = 0; ++c; } }
         } else {
@@ -175,9 +239,10 @@ struct DeviceGuard {
   }
 };
 
-}  // namespace
-
-int hip_image_augment(int device, const ImageAugArgs& a, void* stream) {
+// both entries' launch: the LDS kernel when the images it stages (one, with MIX two) fit the
+// budget and the 16-byte conditions hold, else the global-gather kernel
+template <bool MIX>
+int launch_augment(int device, const AugArgs<MIX>& a, void* stream) {
   DeviceGuard g(device);
   const int64_t total = a.B * a.C * a.out_h * a.out_w;
   const int64_t quads = (total + 3) / 4;
@@ -187,37 +252,48 @@ int hip_image_augment(int device, const ImageAugArgs& a, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t img_bytes = static_cast<int64_t>(a.H) * a.W * a.C;
   const int64_t per = static_cast<int64_t>(a.C) * a.out_h * a.out_w;
-  if (vec && img_bytes <= kAugLdsBytes && img_bytes % 16 == 0 && per % 4 == 0 &&
-      (reinterpret_cast<uintptr_t>(a.src) & 15u) == 0) {
+  const int64_t staged = MIX ? 2 * img_bytes : img_bytes;
+  bool aligned = (reinterpret_cast<uintptr_t>(a.src) & 15u) == 0;
+  if constexpr (MIX) aligned = aligned && (reinterpret_cast<uintptr_t>(a.mix) & 15u) == 0;
+  if (vec && staged <= kAugLdsBytes && img_bytes % 16 == 0 && per % 4 == 0 && aligned) {
     const int g2 = static_cast<int>(std::min<int64_t>(a.B, 65535));
-    const size_t lds = static_cast<size_t>(img_bytes);
+    const size_t lds = static_cast<size_t>(staged);
     if (a.layout == GS_LAYOUT_NCHW) {
       if (a.out_dtype == GS_F32)
-        hipLaunchKernelGGL((augment_lds_kernel<GS_LAYOUT_NCHW, GS_F32>), dim3(g2), dim3(256), lds, s, a);
+        hipLaunchKernelGGL((augment_lds_kernel<GS_LAYOUT_NCHW, GS_F32, MIX>), dim3(g2), dim3(256), lds, s, a);
       else
-        hipLaunchKernelGGL((augment_lds_kernel<GS_LAYOUT_NCHW, GS_BF16>), dim3(g2), dim3(256), lds, s, a);
+        hipLaunchKernelGGL((augment_lds_kernel<GS_LAYOUT_NCHW, GS_BF16, MIX>), dim3(g2), dim3(256), lds, s, a);
     } else {
       if (a.out_dtype == GS_F32)
-        hipLaunchKernelGGL((augment_lds_kernel<GS_LAYOUT_NHWC, GS_F32>), dim3(g2), dim3(256), lds, s, a);
+        hipLaunchKernelGGL((augment_lds_kernel<GS_LAYOUT_NHWC, GS_F32, MIX>), dim3(g2), dim3(256), lds, s, a);
       else
-        hipLaunchKernelGGL((augment_lds_kernel<GS_LAYOUT_NHWC, GS_BF16>), dim3(g2), dim3(256), lds, s, a);
+        hipLaunchKernelGGL((augment_lds_kernel<GS_LAYOUT_NHWC, GS_BF16, MIX>), dim3(g2), dim3(256), lds, s, a);
     }
     HIP_RET(hipGetLastError());
     return GS_OK;
   }
   if (a.layout == GS_LAYOUT_NCHW) {
     if (a.out_dtype == GS_F32)
-      hipLaunchKernelGGL((augment_kernel<GS_LAYOUT_NCHW, GS_F32>), dim3(blocks), dim3(256), 0, s, a, total, vec);
+      hipLaunchKernelGGL((augment_kernel<GS_LAYOUT_NCHW, GS_F32, MIX>), dim3(blocks), dim3(256), 0, s, a, total, vec);
     else
-      hipLaunchKernelGGL((augment_kernel<GS_LAYOUT_NCHW, GS_BF16>), dim3(blocks), dim3(256), 0, s, a, total, vec);
+      hipLaunchKernelGGL((augment_kernel<GS_LAYOUT_NCHW, GS_BF16, MIX>), dim3(blocks), dim3(256), 0, s, a, total, vec);
   } else {
     if (a.out_dtype == GS_F32)
-      hipLaunchKernelGGL((augment_kernel<GS_LAYOUT_NHWC, GS_F32>), dim3(blocks), dim3(256), 0, s, a, total, vec);
+      hipLaunchKernelGGL((augment_kernel<GS_LAYOUT_NHWC, GS_F32, MIX>), dim3(blocks), dim3(256), 0, s, a, total, vec);
     else
-      hipLaunchKernelGGL((augment_kernel<GS_LAYOUT_NHWC, GS_BF16>), dim3(blocks), dim3(256), 0, s, a, total, vec);
+      hipLaunchKernelGGL((augment_kernel<GS_LAYOUT_NHWC, GS_BF16, MIX>), dim3(blocks), dim3(256), 0, s, a, total, vec);
   }
   HIP_RET(hipGetLastError());
   return GS_OK;
+}
+
+}  // namespace
+
+int hip_image_augment(int device, const ImageAugArgs& a, void* stream) {
+  return launch_augment<false>(device, a, stream);
+}
+int hip_image_augment_mix(int device, const ImageMixAugArgs& a, void* stream) {
+  return launch_augment<true>(device, a, stream);
 }
 
 }  // namespace gs

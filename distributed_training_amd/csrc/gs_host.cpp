@@ -550,14 +550,28 @@ int host_eval_accumulate(const void* logits, int dt, const int64_t* labels, int6
   return GS_OK;
 }
 
-// gs_xent_fwd on the host: the rules of include/gsync.h row by row, the sums as PairSums.
+// gs_xent_fwd and (labels_b, lam not null) gs_xent_mix_fwd on the host: the rules of include/gsync.h row by
+// row, the sums as PairSums.
 template <int DT>
-void host_xent_rows(const void* logits, const int64_t* labels, int64_t B, int K, int64_t row_stride,
-                    int64_t ignore_index, float eps, XentRow* rows, double* nll) {
+void host_xent_rows(const void* logits, const int64_t* labels, const int64_t* labels_b, const float* lamv, int64_t B,
+                    int K, int64_t row_stride, int64_t ignore_index, float eps, XentRow* rows, double* nll) {
   for (int64_t row = 0; row < B; ++row) {
-    const int64_t y = labels[row];
+    int64_t y = labels[row];  // the label the rank is counted against
+    const int64_t ya = y;
+    int64_t yb = y;
+    float lam = 1.f;
+    bool one = true;
     nll[row] = 0.0;
-    if (y == ignore_index || y < 0 || y >= K) {
+    if (labels_b) {
+      yb = labels_b[row], lam = lamv[row];
+      const int32_t code = xent_mix_code(ya, yb, lam, K, ignore_index);
+      if (code < 0) {
+        rows[row] = XentRow{0.f, 0.f, 0.f, code};
+        continue;
+      }
+      one = xent_mix_one(ya, yb, lam);
+      y = one ? ya : xent_mix_dominant(ya, yb, lam);
+    } else if (y == ignore_index || y < 0 || y >= K) {
       rows[row] = XentRow{0.f, 0.f, 0.f, y == ignore_index ? kEvalSkip : kEvalBad};
       continue;
     }
@@ -586,16 +600,24 @@ void host_xent_rows(const void* logits, const int64_t* labels, int64_t B, int K,
     }
     const float logS = logf(se.fold(static_cast<uint32_t>(K)));
     const float t = eps != 0.f ? sz.fold(static_cast<uint32_t>(K)) : 0.f;
+    if (!one) {
+      const float za = ldT<DT>(logits, base + ya), zb = ldT<DT>(logits, base + yb);
+      rows[row] = XentRow{xent_mix_loss(m, logS, za, zb, lam, t, K, eps), m, logS, rank};
+      nll[row] = static_cast<double>(xent_mix_loss(m, logS, za, zb, lam, 0.f, 1, 0.f));
+      continue;
+    }
     rows[row] = XentRow{xent_loss(m, logS, zy, t, K, eps), m, logS, rank};
     nll[row] = static_cast<double>((m - zy) + logS);
   }
 }
 
-int host_xent_fwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride,
-                  int64_t ignore_index, float eps, void* rows, void* red, const EvalTopk& topk, void* acc) {
+int host_xent_mix_fwd(const void* logits, int dt, const int64_t* labels, const int64_t* labels_b, const float* lam,
+                      int64_t B, int K, int64_t row_stride, int64_t ignore_index, float eps, void* rows, void* red,
+                      const EvalTopk& topk, void* acc) {
   XentRow* rp = static_cast<XentRow*>(rows);
   std::vector<double> nll(static_cast<size_t>(B));
-  GS_DISPATCH_FLOAT(dt, DT, host_xent_rows<DT>(logits, labels, B, K, row_stride, ignore_index, eps, rp, nll.data()));
+  GS_DISPATCH_FLOAT(dt, DT, host_xent_rows<DT>(logits, labels, labels_b, lam, B, K, row_stride, ignore_index, eps, rp,
+                                               nll.data()));
   int64_t* ap = B > 0 ? static_cast<int64_t*>(acc) : nullptr;
   int64_t counted = 0, bad = 0;
   double total = 0.0, total_nll = 0.0;
@@ -624,8 +646,8 @@ int host_xent_fwd(const void* logits, int dt, const int64_t* labels, int64_t B, 
 }
 
 template <int DT>
-void host_xent_grad(const void* logits, const int64_t* labels, int64_t B, int K, int64_t row_stride, float eps,
-                    int reduction, const XentRow* rows, const XentRed* red, const float* grad_out, void* dlogits,
+void host_xent_grad(const void* logits, const int64_t* labels, const int64_t* labels_b, const float* lamv, int64_t B,
+                    int K, int64_t row_stride, float eps, int reduction, const XentRow* rows, const XentRed* red, const float* grad_out, void* dlogits,
                     int64_t d_row_stride) {
   const float q_off = eps / static_cast<float>(K);
   const float q_on = (1.f - eps) + q_off;
@@ -637,17 +659,26 @@ void host_xent_grad(const void* logits, const int64_t* labels, int64_t B, int K,
       continue;
     }
     const int64_t y = labels[row];
+    int64_t yb = -1;  // a mixed row's second label, with targets qa at y and qb at yb
+    float qa = q_on, qb = q_off;
+    if (labels_b && !xent_mix_one(y, labels_b[row], lamv[row])) {
+      yb = labels_b[row];
+      qa = xent_mix_q(eps, lamv[row], q_off);
+      qb = xent_mix_q(eps, 1.f - lamv[row], q_off);
+    }
     const float g = grad_out[reduction == kXentNone ? row : 0];
     const float c = reduction == kXentMean ? g / static_cast<float>(red->counted) : g;
-    for (int j = 0; j < K; ++j)
-      stT<DT>(dlogits, db + j, xent_grad(ldT<DT>(logits, zb + j), w.m, w.logS, j == y ? q_on : q_off, c));
+    for (int j = 0; j < K; ++j) {
+      const float q = j == y ? qa : j == yb ? qb : q_off;
+      stT<DT>(dlogits, db + j, xent_grad(ldT<DT>(logits, zb + j), w.m, w.logS, q, c));
+    }
   }
 }
 
-int host_xent_bwd(const void* logits, int dt, const int64_t* labels, int64_t B, int K, int64_t row_stride, float eps,
-                  int reduction, const void* rows, const void* red, const float* grad_out, void* dlogits,
-                  int64_t d_row_stride) {
-  GS_DISPATCH_FLOAT(dt, DT, host_xent_grad<DT>(logits, labels, B, K, row_stride, eps, reduction,
+int host_xent_mix_bwd(const void* logits, int dt, const int64_t* labels, const int64_t* labels_b, const float* lam,
+                      int64_t B, int K, int64_t row_stride, float eps, int reduction, const void* rows,
+                      const void* red, const float* grad_out, void* dlogits, int64_t d_row_stride) {
+  GS_DISPATCH_FLOAT(dt, DT, host_xent_grad<DT>(logits, labels, labels_b, lam, B, K, row_stride, eps, reduction,
                                                static_cast<const XentRow*>(rows), static_cast<const XentRed*>(red),
                                                grad_out, dlogits, d_row_stride));
   return GS_OK;

@@ -37,7 +37,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Iterator, Sequence
+from typing import Iterator, NamedTuple, Sequence
 
 import numpy as np
 import torch
@@ -177,16 +177,144 @@ TRAIN_TRANSFORM = PadFlipCrop(4, True, 32)
 TEST_TRANSFORM = PadFlipCrop(0, False, None)
 
 
+class MixedTarget(NamedTuple):
+    """The target of a mixed batch: row ``i`` is ``labels_a[i]`` with weight ``lam[i]`` and
+    ``labels_b[i]`` with weight ``1 - lam[i]``.  int64 ``[B]``, int64 ``[B]``, float32 ``[B]``, on the
+    batch's device.  ``loss.cross_entropy`` and ``CrossEntropyLoss`` take it in place of the labels."""
+    labels_a: torch.Tensor
+    labels_b: torch.Tensor
+    lam: torch.Tensor
+
+
+_LAM_ONE = int(np.float32(1.0).view(np.int32))
+
+
+class MixUpCutMix:
+    """MixUp (Zhang et al., 2018) and CutMix (Yun et al., 2019) for :class:`DeviceDataLoader`: it draws, per
+    batch, the ``[B, 4]`` int32 records ``gs_image_augment_mix`` (include/gsync.h) applies inside the input
+    kernel: ``(partner, lam as fp32 bits, y0 | y1 << 16, x0 | x1 << 16)``.
+
+    ``mixup_alpha`` / ``cutmix_alpha``: the Beta(alpha, alpha) parameter of each; 0 turns that one off, both
+    0 is an error.  ``prob``: the chance that a batch (``mode="batch"``) or a sample (``mode="elem"``) is
+    mixed at all.  ``switch_prob``: with both on, the chance of CutMix.
+
+    The draws come from this object's own ``numpy.random.Generator`` (PCG64 seeded ``[seed, rank]``;
+    ``rank=None``: the process group's rank if one is initialised, else 0), never from torch's generators.
+    ``state_dict()`` / ``load_state_dict()`` carry the bit generator's state.
+
+    Draw order per batch of ``B`` samples with output extent ``oh x ow``, ``mode="batch"``:
+
+    1. ``u_apply = rng.random()``
+    2. ``u_switch = rng.random()`` (both always drawn)
+    3. ``u_apply >= prob``: identity records, nothing else is drawn
+    4. CutMix if both alphas are positive and ``u_switch < switch_prob``, or if only ``cutmix_alpha`` is
+       positive; else MixUp; ``a`` is the chosen one's alpha
+    5. ``lam = rng.beta(a, a)``
+    6. CutMix only: ``cy = rng.integers(oh)``, then ``cx = rng.integers(ow)``
+    7. ``perm = rng.permutation(B)``: sample ``i``'s partner is batch position ``perm[i]``
+
+    ``mode="elem"`` makes the same draws as length-``B`` vectors in the same order and never stops early:
+    ``u_apply = rng.random(B)``, ``u_switch = rng.random(B)``, ``lam = rng.beta(a, a)`` with ``a`` the
+    vector of each sample's chosen alpha (1.0 for a sample with ``u_apply >= prob``, whose draws are then
+    unused), then, if ``cutmix_alpha`` is positive, ``cy = rng.integers(oh, size=B)`` and
+    ``cx = rng.integers(ow, size=B)``, then one ``perm = rng.permutation(B)``.
+
+    MixUp's record is ``(perm[i], fp32(lam), 0, 0)``.  CutMix's box is the paper's ``rand_bbox`` on the output
+    extent: ``r = sqrt(1 - lam)``, ``ch = int(oh * r)``, ``cw = int(ow * r)``, ``y0, y1 = clip(cy -/+ ch // 2,
+    0, oh)``, ``x0, x1`` likewise, and the weight is corrected to the box, ``lam = 1 - (y1 - y0) * (x1 - x0) /
+    (oh * ow)`` in double, rounded to fp32.  An empty box, and a sample that is not mixed, is the identity
+    record ``(i, fp32(1), 0, 0)``."""
+
+    def __init__(self, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, prob: float = 1.0,
+                 switch_prob: float = 0.5, mode: str = "batch", seed: int = 0, rank: int | None = None):
+        if mixup_alpha < 0 or cutmix_alpha < 0 or not (mixup_alpha > 0 or cutmix_alpha > 0):
+            raise ValueError("MixUpCutMix: mixup_alpha and cutmix_alpha must be >= 0 and not both 0")
+        if mode not in ("batch", "elem"):
+            raise ValueError("MixUpCutMix: mode must be 'batch' or 'elem'")
+        if not (0.0 <= prob <= 1.0 and 0.0 <= switch_prob <= 1.0):
+            raise ValueError("MixUpCutMix: prob and switch_prob must be in [0, 1]")
+        if rank is None:
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob, self.mode = float(prob), float(switch_prob), mode
+        self.seed, self.rank = int(seed), int(rank)
+        self.rng = np.random.Generator(np.random.PCG64([self.seed, self.rank]))
+
+    def state_dict(self) -> dict:
+        return {"bit_generator": self.rng.bit_generator.state}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.rng.bit_generator.state = state["bit_generator"]
+
+    def _cutmix(self, u_switch):
+        """CutMix (True) or MixUp (False) for the draw(s) ``u_switch``"""
+        if self.mixup_alpha > 0 and self.cutmix_alpha > 0:
+            return u_switch < self.switch_prob
+        return np.full(np.shape(u_switch), self.cutmix_alpha > 0)
+
+    def records(self, B: int, oh: int, ow: int) -> np.ndarray:
+        """the next batch's ``[B, 4]`` int32 records (see the class's docstring for the draws)"""
+        rng = self.rng
+        rec = np.zeros((B, 4), dtype=np.int32)
+        rec[:, 0] = np.arange(B)
+        rec[:, 1] = _LAM_ONE
+        if self.mode == "batch":
+            u_apply, u_switch = rng.random(), rng.random()
+            if u_apply >= self.prob:
+                return rec
+            is_cut = bool(self._cutmix(u_switch))
+            a = self.cutmix_alpha if is_cut else self.mixup_alpha
+            cut = np.full(B, is_cut)
+            lam = np.full(B, rng.beta(a, a))
+            cy = cx = None
+            if is_cut:
+                cy = np.full(B, rng.integers(oh))
+                cx = np.full(B, rng.integers(ow))
+            apply = np.ones(B, dtype=bool)
+        else:
+            u_apply, u_switch = rng.random(B), rng.random(B)
+            apply = u_apply < self.prob
+            cut = np.asarray(self._cutmix(u_switch), dtype=bool) & apply
+            a = np.where(apply, np.where(cut, self.cutmix_alpha, self.mixup_alpha), 1.0)
+            lam = rng.beta(a, a)
+            cy = cx = None
+            if self.cutmix_alpha > 0:
+                cy, cx = rng.integers(oh, size=B), rng.integers(ow, size=B)
+        perm = rng.permutation(B)
+        lam32 = lam.astype(np.float32)
+        ys = np.zeros(B, dtype=np.int64)
+        xs = np.zeros(B, dtype=np.int64)
+        if cy is not None:
+            r = np.sqrt(1.0 - lam)
+            ch, cw = (oh * r).astype(np.int64), (ow * r).astype(np.int64)
+            y0, y1 = np.clip(cy - ch // 2, 0, oh), np.clip(cy + ch // 2, 0, oh)
+            x0, x1 = np.clip(cx - cw // 2, 0, ow), np.clip(cx + cw // 2, 0, ow)
+            area = (y1 - y0) * (x1 - x0)
+            boxed = cut & (area > 0)
+            apply = apply & (boxed | ~cut)  # an empty box is the identity
+            lam32 = np.where(cut, (1.0 - area / float(oh * ow)).astype(np.float32), lam32)
+            ys = np.where(boxed, y0 | (y1 << 16), 0)
+            xs = np.where(boxed, x0 | (x1 << 16), 0)
+        rec[:, 0] = np.where(apply, perm, rec[:, 0])
+        rec[:, 1] = np.where(apply, lam32.view(np.int32), _LAM_ONE)
+        rec[:, 2] = ys.astype(np.uint32).view(np.int32)
+        rec[:, 3] = xs.astype(np.uint32).view(np.int32)
+        return rec
+
+
 class DeviceDataLoader:
     """``DataLoader(dataset, batch_size, shuffle=False, sampler=..., drop_last=...)``
     over an :class:`ImageDataset`, yielding ``(images, labels)`` on the
     dataset's device: images float32 (or ``out_dtype``) ``[B, C, h, w]`` in
-    ``memory_format``, labels int64 ``[B]``."""
+    ``memory_format``, labels int64 ``[B]``.
+
+    ``mix``: a :class:`MixUpCutMix`; the batch is then mixed inside the same kernel
+    (``gs_image_augment_mix``) and the loader yields ``(images, MixedTarget)``."""
 
     def __init__(self, dataset: ImageDataset, batch_size: int = 1, shuffle: bool = False, sampler=None,
                  drop_last: bool = False, transform: PadFlipCrop = TEST_TRANSFORM,
                  out_dtype: torch.dtype = torch.float32, memory_format=torch.contiguous_format,
-                 generator: torch.Generator | None = None):
+                 generator: torch.Generator | None = None, mix: MixUpCutMix | None = None):
         if shuffle and sampler is not None:
             raise ValueError("sampler option is mutually exclusive with shuffle")
         if shuffle:
@@ -202,6 +330,7 @@ class DeviceDataLoader:
         self.out_dtype = out_dtype
         self.memory_format = memory_format
         self.generator = generator
+        self.mix = mix
         self.device = dataset.device
         self._kind = L.GS_DEV_HIP if self.device.type == "cuda" else L.GS_DEV_HOST
         if self._kind == L.GS_DEV_HIP and not L.available():
@@ -266,6 +395,22 @@ class DeviceDataLoader:
                               memory_format=self.memory_format)
             layout = L.GS_LAYOUT_NHWC if (self.memory_format == torch.channels_last and B > 0) else L.GS_LAYOUT_NCHW
             labels = torch.empty(B, dtype=torch.int64, device=self.device)
+            if self.mix is not None:
+                # the records travel as params does: a pinned block per batch, a non-blocking copy
+                rec = torch.empty((B, 4), dtype=torch.int32, pin_memory=self._kind == L.GS_DEV_HIP)
+                rec.numpy()[...] = self.mix.records(B, self.oh, self.ow)
+                drec = rec.to(self.device, non_blocking=True) if self._kind == L.GS_DEV_HIP else rec
+                labels_b = torch.empty(B, dtype=torch.int64, device=self.device)
+                lam = torch.empty(B, dtype=torch.float32, device=self.device)
+                L.check(L.lib().gs_image_augment_mix(self._kind, self.device.index or 0, ds.images.data_ptr(),
+                                                      ds.labels.data_ptr(), ds.n, ds.H, ds.W, ds.C,
+                                                      self.transform.pad, self.oh, self.ow, dparams.data_ptr(),
+                                                      drec.data_ptr(), B, out.data_ptr(),
+                                                      L.gs_dtype(self.out_dtype), layout, labels.data_ptr(),
+                                                      labels_b.data_ptr(), lam.data_ptr(), stream),
+                        "gs_image_augment_mix")
+                yield out, MixedTarget(labels, labels_b, lam)
+                continue
             L.check(L.lib().gs_image_augment(self._kind, self.device.index or 0, ds.images.data_ptr(),
                                               ds.labels.data_ptr(), ds.n, ds.H, ds.W, ds.C, self.transform.pad,
                                               self.oh, self.ow, dparams.data_ptr(), B, out.data_ptr(),

@@ -17,6 +17,14 @@ Differences from torch, both on the fused path only:
 * a label outside ``[0, K)`` that is not ``ignore_index`` does not assert on the device: the
   reduced loss is NaN (``"none"``: that row's loss is 0) and the row's gradient is zero.
 
+A ``MixedTarget`` (data.py: the pair targets of a MixUp / CutMix batch, two labels and one weight per row)
+in place of the labels runs ``gs_xent_mix_fwd`` / ``gs_xent_mix_bwd`` under the same conditions, in the same
+three launches; the three tensors are read on the device, so a captured criterion replays with new targets.
+A row with ``lam == 1`` or equal labels is bit for bit the one-label row.  ``metrics`` count top-k against a
+row's dominant label (``a`` if ``lam >= 0.5`` else ``b``) and add the unsmoothed mixed loss.  Off the fused
+path a ``MixedTarget`` is the torch composition ``lam * CE(z, a, "none") + (1 - lam) * CE(z, b, "none")``
+reduced over the counted rows (those where neither label is ``ignore_index``).
+
 Everything else (class-probability targets, ``weight``, inputs of more than two dimensions, the
 legacy ``size_average`` / ``reduce`` arguments) and ``GSYNC_FUSED_LOSS=0`` run
 ``F.cross_entropy``.  ``last_path`` names the path of the last call: ``"fused"`` or ``"torch"``.
@@ -36,6 +44,7 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
+from .data import MixedTarget
 from .evaluation import Metrics
 
 last_path: str | None = None
@@ -58,17 +67,27 @@ class _FusedCrossEntropy(torch.autograd.Function):
     def forward(ctx, logits, target, ignore_index, eps, reduction, metrics):
         B, K = logits.shape
         z, stride = _rows_of(logits.detach())
-        labels = target.to(torch.int64).contiguous()
+        mixed = isinstance(target, MixedTarget)
+        if mixed:
+            labels = target.labels_a.to(torch.int64).contiguous()
+            pair = (target.labels_b.to(torch.int64).contiguous(), target.lam.contiguous())
+        else:
+            labels, pair = target.to(torch.int64).contiguous(), ()
         # rows (16 bytes each), then the 16 bytes of the reduced result
         scratch = torch.empty(4 * (B + 1), dtype=torch.float32, device=z.device)
         kind, dt, stream = L.device_kind(z), L.gs_dtype(z.dtype), L.stream_ptr(z.device)
         red_ptr = scratch.data_ptr() + 16 * B
         topk, n_topk, acc = (None, 0, None) if metrics is None else (metrics._topk, len(metrics.topk),
                                                                       metrics._acc.data_ptr())
-        L.check(L.lib().gs_xent_fwd(kind, z.data_ptr(), dt, labels.data_ptr(), B, K, stride, ignore_index, eps,
-                                    scratch.data_ptr(), red_ptr, topk, n_topk, acc, stream), "gs_xent_fwd")
+        if mixed:
+            L.check(L.lib().gs_xent_mix_fwd(kind, z.data_ptr(), dt, labels.data_ptr(), pair[0].data_ptr(),
+                                            pair[1].data_ptr(), B, K, stride, ignore_index, eps, scratch.data_ptr(),
+                                            red_ptr, topk, n_topk, acc, stream), "gs_xent_mix_fwd")
+        else:
+            L.check(L.lib().gs_xent_fwd(kind, z.data_ptr(), dt, labels.data_ptr(), B, K, stride, ignore_index, eps,
+                                        scratch.data_ptr(), red_ptr, topk, n_topk, acc, stream), "gs_xent_fwd")
         if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(z, labels, scratch)
+            ctx.save_for_backward(z, labels, scratch, *pair)
             ctx.args = (stride, ignore_index, eps, reduction)
         if reduction == 0:
             return scratch[:4 * B].view(B, 4)[:, 0]
@@ -77,24 +96,56 @@ class _FusedCrossEntropy(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        z, labels, scratch = ctx.saved_tensors
+        z, labels, scratch, *pair = ctx.saved_tensors
         stride, ignore_index, eps, reduction = ctx.args
         B, K = z.shape
         g = grad_out.to(torch.float32).contiguous()
         dz = torch.empty((B, K), dtype=z.dtype, device=z.device)
+        if pair:
+            L.check(L.lib().gs_xent_mix_bwd(L.device_kind(z), z.data_ptr(), L.gs_dtype(z.dtype), labels.data_ptr(),
+                                            pair[0].data_ptr(), pair[1].data_ptr(), B, K, stride, ignore_index, eps,
+                                            reduction, scratch.data_ptr(), scratch.data_ptr() + 16 * B, g.data_ptr(),
+                                            dz.data_ptr(), K, L.stream_ptr(z.device)), "gs_xent_mix_bwd")
+            return dz, None, None, None, None, None
         L.check(L.lib().gs_xent_bwd(L.device_kind(z), z.data_ptr(), L.gs_dtype(z.dtype), labels.data_ptr(), B, K, stride,
                                     ignore_index, eps, reduction, scratch.data_ptr(), scratch.data_ptr() + 16 * B,
                                     g.data_ptr(), dz.data_ptr(), K, L.stream_ptr(z.device)), "gs_xent_bwd")
         return dz, None, None, None, None, None
 
 
+def _labels_ok(input, t) -> bool:
+    return t.dim() == 1 and t.dtype in _INTS and t.shape[0] == input.shape[0] and t.device == input.device
+
+
 def _fusable(input, target, weight, size_average, reduce, reduction, label_smoothing) -> bool:
+    if isinstance(target, MixedTarget):
+        lam = target.lam
+        target_ok = (input.dim() == 2 and _labels_ok(input, target.labels_a) and _labels_ok(input, target.labels_b)
+                     and lam.dim() == 1 and lam.dtype == torch.float32 and lam.shape[0] == input.shape[0]
+                     and lam.device == input.device)
+    else:
+        target_ok = input.dim() == 2 and _labels_ok(input, target)
     return (os.environ.get("GSYNC_FUSED_LOSS", "1") != "0"
             and weight is None and size_average is None and reduce is None and reduction in _REDUCTIONS
             and input.dim() == 2 and input.shape[1] >= 1 and input.dtype in _FLOATS
-            and input.device.type in ("cpu", "cuda")
-            and target.dim() == 1 and target.dtype in _INTS and target.shape[0] == input.shape[0]
-            and target.device == input.device and 0.0 <= label_smoothing <= 1.0)
+            and input.device.type in ("cpu", "cuda") and target_ok and 0.0 <= label_smoothing <= 1.0)
+
+
+def _torch_mixed(input, target, weight, size_average, ignore_index, reduce, reduction, label_smoothing):
+    """the torch composition of a MixedTarget: the two per-row losses blended, reduced over the counted rows"""
+    if size_average is not None or reduce is not None:
+        reduction = torch.nn._reduction.legacy_get_string(size_average, reduce)
+    a, b = target.labels_a, target.labels_b
+    lam = target.lam.to(input.dtype if input.dtype.is_floating_point else torch.float32)
+    la = F.cross_entropy(input, a, weight, ignore_index=ignore_index, reduction="none", label_smoothing=label_smoothing)
+    lb = F.cross_entropy(input, b, weight, ignore_index=ignore_index, reduction="none", label_smoothing=label_smoothing)
+    counted = (a != ignore_index) & (b != ignore_index)
+    rows = torch.where(counted, lam * la + (1 - lam) * lb, torch.zeros_like(la))
+    if reduction == "none":
+        return rows
+    if reduction == "sum":
+        return rows.sum()
+    return rows.sum() / counted.sum()
 
 
 def cross_entropy(input, target, weight=None, size_average=None, ignore_index=-100, reduce=None, reduction="mean",
@@ -111,6 +162,12 @@ def cross_entropy(input, target, weight=None, size_average=None, ignore_index=-1
         return _FusedCrossEntropy.apply(input, target, int(ignore_index), float(label_smoothing),
                                         _REDUCTIONS[reduction], metrics)
     last_path = "torch"
+    if isinstance(target, MixedTarget):
+        if metrics is not None:
+            dominant = torch.where(target.lam >= 0.5, target.labels_a, target.labels_b)
+            skipped = (target.labels_a == ignore_index) | (target.labels_b == ignore_index)
+            metrics.update(input.detach(), torch.where(skipped, torch.full_like(dominant, ignore_index), dominant))
+        return _torch_mixed(input, target, weight, size_average, ignore_index, reduce, reduction, label_smoothing)
     if metrics is not None:
         metrics.update(input.detach(), target)
     return F.cross_entropy(input, target, weight, size_average, ignore_index, reduce, reduction, label_smoothing)

@@ -17,6 +17,10 @@ sample counted once across the ranks) and prints one line on rank 0.
 ``--fused-loss`` swaps ``nn.CrossEntropyLoss`` for ``distributed_training_amd.CrossEntropyLoss`` with a
 ``Metrics``: the loop then never reads the loss from the device, and the epoch's mean (unsmoothed) loss and
 top-1 over all ranks come from one ``compute()`` at its end.  ``--label-smoothing`` goes to either criterion.
+
+``--mixup ALPHA`` / ``--cutmix ALPHA`` (``--mix-prob P``) mix every training batch inside the input kernel
+(``DeviceDataLoader(mix=MixUpCutMix(...))``); the loader then yields a ``MixedTarget``, which
+``distributed_training_amd.CrossEntropyLoss`` takes in place of the labels, so that criterion is used.
 """
 from __future__ import annotations
 
@@ -31,12 +35,13 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from distributed_training_amd import DDP, CrossEntropyLoss, FusedAdam as Adam, Metrics, evaluate  # noqa: E402
+from distributed_training_amd import (DDP, CrossEntropyLoss, FusedAdam as Adam, Metrics, MixUpCutMix,  # noqa: E402
+                                      evaluate)
 from distributed_training_amd import data as D  # noqa: E402
 from distributed_training_amd.resnet import MODELS  # noqa: E402
 
 
-def build_dataloader(batch_size: int, device, synthetic_n: int = 50000):
+def build_dataloader(batch_size: int, device, synthetic_n: int = 50000, mix=None):
     """R:ddp_train.py:25-48 on device-resident data."""
     data_path = os.environ.get("DATA", "../data")
     try:
@@ -45,7 +50,9 @@ def build_dataloader(batch_size: int, device, synthetic_n: int = 50000):
     except FileNotFoundError:
         train = D.ImageDataset.synthetic(synthetic_n, seed=0, device=device)
         test = D.ImageDataset.synthetic(max(1, synthetic_n // 5), seed=1, device=device)
-    return D.build_dataloader(batch_size, train, test)
+    train_loader, test_loader = D.build_dataloader(batch_size, train, test)
+    train_loader.mix = mix  # the training batches only
+    return train_loader, test_loader
 
 
 def train_epoch(epoch, num_epochs, model, optimizer, criterion, train_dataloader, max_steps=None):
@@ -73,7 +80,7 @@ def train_epoch(epoch, num_epochs, model, optimizer, criterion, train_dataloader
 
 def ddp(rank, world_size, num_epochs, learning_rate, batch_size, device_type="cuda", max_steps=None,
         synthetic_n=50000, port=12355, result=None, local_rank=None, run_eval=False, label_smoothing=0.0,
-        fused_loss=False):
+        fused_loss=False, mixup=0.0, cutmix=0.0, mix_prob=1.0):
     """R:ddp_train.py:94-105 (ddp_setup :79-85 with the backend chosen by device).  ``run_eval``: after each
     epoch, evaluate on the test loader the reference builds and never drains (:47)."""
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -87,10 +94,13 @@ def ddp(rank, world_size, num_epochs, learning_rate, batch_size, device_type="cu
         dist.init_process_group("gloo", rank=rank, world_size=world_size)
     torch.manual_seed(0)
     model = DDP(MODELS["resnet18"](num_classes=10).to(device))
-    train_dataloader, test_dataloader = build_dataloader(batch_size, device, synthetic_n)
+    mix = MixUpCutMix(mixup, cutmix, prob=mix_prob, rank=rank) if (mixup > 0 or cutmix > 0) else None
+    train_dataloader, test_dataloader = build_dataloader(batch_size, device, synthetic_n, mix)
     optimizer = Adam(model.parameters(), lr=learning_rate)
     if fused_loss:
         criterion = CrossEntropyLoss(label_smoothing=label_smoothing, metrics=Metrics(topk=(1,), device=device))
+    elif mix is not None:
+        criterion = CrossEntropyLoss(label_smoothing=label_smoothing)  # nn.CrossEntropyLoss takes no MixedTarget
     elif label_smoothing:
         criterion = nn.CrossEntropyLoss(label_smoothing=label_smoothing)
     else:
@@ -126,16 +136,19 @@ def main():
     ap.add_argument("--label-smoothing", type=float, default=0.0)
     ap.add_argument("--fused-loss", action="store_true",
                     help="the fused criterion with device-side running metrics instead of nn.CrossEntropyLoss")
+    ap.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA", help="MixUp with Beta(ALPHA, ALPHA); 0: off")
+    ap.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA", help="CutMix with Beta(ALPHA, ALPHA); 0: off")
+    ap.add_argument("--mix-prob", type=float, default=1.0, metavar="P", help="the chance that a batch is mixed")
     a = ap.parse_args()
     if "RANK" in os.environ:  # torchrun
         ws = int(os.environ["WORLD_SIZE"])
         ddp(int(os.environ["RANK"]), ws, a.epochs, 1e-3 * ws, a.batch_size, a.device, a.max_steps,
             local_rank=int(os.environ.get("LOCAL_RANK", "0")), run_eval=a.eval, label_smoothing=a.label_smoothing,
-            fused_loss=a.fused_loss)
+            fused_loss=a.fused_loss, mixup=a.mixup, cutmix=a.cutmix, mix_prob=a.mix_prob)
     else:
         ws = a.world_size
         mp.spawn(ddp, args=(ws, a.epochs, 1e-3 * ws, a.batch_size, a.device, a.max_steps, 50000, 12355, None, None,
-                            a.eval, a.label_smoothing, a.fused_loss), nprocs=ws)
+                            a.eval, a.label_smoothing, a.fused_loss, a.mixup, a.cutmix, a.mix_prob), nprocs=ws)
 
 
 if __name__ == "__main__":

@@ -705,6 +705,31 @@ int gs_crop_flip_params(const int64_t* indices, int64_t B, int in_h, int in_w, i
 int gs_image_augment(int device_kind, int device, const uint8_t* src, const int64_t* labels, int64_t n_src,
                      int H, int W, int C, int pad, int out_h, int out_w, const int32_t* params, int64_t B,
                      void* out, int out_dtype, int out_layout, int64_t* out_labels, void* stream);
+/* gs_image_augment with MixUp / CutMix (Zhang et al. 2018; Yun et al. 2019) in the same launch.
+ * mix: [B, 4] int32 beside params, one record per batch position i:
+ *   (partner, lam as fp32 bits, y0 | y1 << 16, x0 | x1 << 16)
+ * partner is a batch position; its image is that position's augmented image, made with its own
+ * params record.  With a = the sample's pixel, b = the partner's pixel at the same (c, y, x) and
+ * lam1 = 1.f - lam, an output element is
+ *   a non-empty box (y0 < y1 and x0 < x1):  b inside [y0, y1) x [x0, x1), a outside
+ *   an empty box, lam != 1:                 a * lam + b * lam1, each multiply and the add rounded
+ *                                           once in fp32, no fma
+ *   an empty box and lam == 1, or partner == i:  a; the partner's image is not read
+ * and the bf16 cast (round to nearest even) follows the blend.  out_labels[i] is the sample's
+ * label, out_labels_b[i] the partner's, out_lam[i] = lam (each nullable).
+ * GS_DEV_HOST rejects with GS_EINVAL, before writing anything, what gs_image_augment rejects and
+ * a partner outside [0, B), lam outside [0, 1] or NaN, a box with y0 > y1, y1 > out_h, x0 > x1
+ * or x1 > out_w; out_h and out_w are at most 65535.  GS_DEV_HIP cannot read the records on the
+ * host: a partner outside [0, B) or such a lam makes the sample its own partner (out_lam = 1,
+ * out_labels_b = out_labels), a box is clamped to the output, and nothing outside the image
+ * set or the batch is read; mix is 16-byte aligned.  One launch on `stream`: one workgroup per
+ * sample that stages the sample's image in LDS, and the partner's behind it when the record
+ * needs it, if two images fit 48 KiB and gs_image_augment's alignment conditions hold; the
+ * global-gather kernel with the same arithmetic otherwise. */
+int gs_image_augment_mix(int device_kind, int device, const uint8_t* src, const int64_t* labels, int64_t n_src,
+                         int H, int W, int C, int pad, int out_h, int out_w, const int32_t* params,
+                         const int32_t* mix, int64_t B, void* out, int out_dtype, int out_layout,
+                         int64_t* out_labels, int64_t* out_labels_b, float* out_lam, void* stream);
 
 /* ======================================================================
  * NHWC BatchNorm backward fused with the ReLU mask and the residual add
@@ -913,6 +938,33 @@ int gs_xent_fwd(int device_kind, const void* logits, int logits_dtype, const int
 int gs_xent_bwd(int device_kind, const void* logits, int logits_dtype, const int64_t* labels, int64_t B, int64_t K,
                 int64_t row_stride, int64_t ignore_index, float label_smoothing, int reduction, const void* rows,
                 const void* red, const float* grad_out, void* dlogits, int64_t d_row_stride, void* stream);
+/* gs_xent_fwd for pair targets (MixUp / CutMix): row r has labels a = labels_a[r], b = labels_b[r]
+ * and a's weight lam = lam[r] (fp32 [B]), all three where device_kind says and read by the
+ * kernels only, so a captured graph replays with new targets.  Everything not said here is
+ * gs_xent_fwd's.  A row is
+ *   skipped (code -1)  if a or b is ignore_index;
+ *   bad (code -2)      else if a or b is outside [0, K), or lam is outside [0, 1] or NaN;
+ *   a one-label row    else if lam == 1 or a == b: exactly gs_xent_fwd's row for label a, the
+ *                      same expressions and so the same 16 bytes;
+ *   a mixed row        otherwise, with loss(y) gs_xent_fwd's loss for label y and lam1 = 1 - lam:
+ *                        loss = lam * loss(a) + lam1 * loss(b), each operation rounded once;
+ *                        code = the rank of the dominant label, a if lam >= 0.5 else b.
+ * acc's loss word is advanced by the same expression at eps = 0, its top-k hits by code.
+ * GS_DEV_HIP: two launches, as gs_xent_fwd.  GS_EINVAL: as gs_xent_fwd, and a null or
+ * misaligned labels_b (8 bytes) or lam (4 bytes). */
+int gs_xent_mix_fwd(int device_kind, const void* logits, int logits_dtype, const int64_t* labels_a,
+                    const int64_t* labels_b, const float* lam, int64_t B, int64_t K, int64_t row_stride,
+                    int64_t ignore_index, float label_smoothing, void* rows, void* red, const int32_t* topk,
+                    int n_topk, void* acc, void* stream);
+/* The gradient of that loss: gs_xent_bwd with, for a mixed row,
+ *   q_j = q_off, (1 - eps) * lam + q_off at j == a, (1 - eps) * lam1 + q_off at j == b
+ * each operation rounded once; a one-label row's q is gs_xent_bwd's for label a, and so are
+ * its gradient's bits.  labels_a, labels_b and lam are what the forward saw; the row scratch
+ * stays 16 bytes.  One launch. */
+int gs_xent_mix_bwd(int device_kind, const void* logits, int logits_dtype, const int64_t* labels_a,
+                    const int64_t* labels_b, const float* lam, int64_t B, int64_t K, int64_t row_stride,
+                    int64_t ignore_index, float label_smoothing, int reduction, const void* rows, const void* red,
+                    const float* grad_out, void* dlogits, int64_t d_row_stride, void* stream);
 
 #ifdef __cplusplus
 }
