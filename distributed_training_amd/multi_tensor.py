@@ -150,6 +150,19 @@ class TensorListPlan:
             "gs_unpack",
         )
 
+    def unpack_check(self, flat: torch.Tensor, dst_slot, dst_dtype, found_inf: torch.Tensor, stream=None):
+        """:meth:`unpack` with the fused AMP inf check (gs_unpack_check): ``found_inf`` (a
+        1-element fp32 tensor where the plan runs) becomes 1 when a written value, rounded to
+        ``dst_dtype``, is not finite, and is left alone otherwise — the flag accumulates."""
+        if found_inf.dtype != torch.float32 or found_inf.numel() < 1 or \
+                (found_inf.device.type == "cuda") != (self.kind == L.GS_DEV_HIP):
+            raise ValueError("found_inf: fp32, where the plan runs")
+        L.check(
+            L.lib().gs_unpack_check(self.handle, flat.data_ptr(), L.gs_dtype(flat.dtype), dst_slot,
+                                    L.gs_dtype(dst_dtype), found_inf.data_ptr(), self._stream(stream)),
+            "gs_unpack_check",
+        )
+
     def scale(self, slot, dtype, s, mode=L.GS_SCALE_MUL, stream=None):
         L.check(L.lib().gs_scale(self.handle, slot, L.gs_dtype(dtype), float(s), mode, self._stream(stream)),
                 "gs_scale")
