@@ -388,6 +388,55 @@ def main():
                 augment_plus_torch_batched_avg_ms=c_batched, ratio_to_augment=f_ms[0] / p_ms[0],
                 ratio_to_augment_plus_torch=f_ms[0] / c_ms[0])
         del ds
+    # the resize-based input step (gs_image_resample: RandomResizedCrop + flip + ToTensor + Normalize + bf16 NHWC in one
+    # launch) at B = 256, beside the torch composition on the same records (per-sample slice + F.interpolate + flip into
+    # an fp32 batch, then one normalise + cast) and a plain device copy that moves the same number of bytes
+    if want("resample"):
+        import ctypes
+
+        import numpy as np
+
+        from distributed_training_amd import data as D
+
+        Br = 256
+        st = torch.cuda.current_stream().cuda_stream
+        for (Hs, n_img, osz) in ((256, 1024, 224), (64, 8192, 56)):
+            ds = D.ImageDataset.synthetic(n_img, H=Hs, W=Hs, device=dev, seed=0)
+            tf = D.RandomResizedCropFlip(osz, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), seed=0, rank=0)
+            recs = tf.records(np.random.default_rng(Hs).integers(0, n_img, Br), Hs, Hs)
+            drec = torch.from_numpy(recs).to(dev)
+            box = [(int(r[0]), int(r[1]), int(r[2]) & 0xFFFF, (int(r[2]) >> 16) & 0xFFFF, int(r[3]) & 0xFFFF,
+                    (int(r[3]) >> 16) & 0xFFFF) for r in recs]
+            xr = torch.empty((Br, 3, osz, osz), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
+            lr_ = torch.empty(Br, dtype=torch.int64, device=dev)
+            c_mean, c_std = (ctypes.c_float * 3)(*tf.mean), (ctypes.c_float * 3)(*tf.std)
+            t_mean = torch.tensor(tf.mean, device=dev).view(1, 3, 1, 1) * 255
+            t_std = torch.tensor(tf.std, device=dev).view(1, 3, 1, 1) * 255
+            tmp = torch.empty((Br, 3, osz, osz), device=dev)
+            alg = sum(b[4] * b[5] * 3 for b in box) + Br * 3 * osz * osz * 2
+            ca, cb = (torch.empty(alg // 2, dtype=torch.uint8, device=dev) for _ in range(2))
+
+            def fused():
+                L.check(L.lib().gs_image_resample(L.GS_DEV_HIP, 0, ds.images.data_ptr(), ds.labels.data_ptr(), ds.n, Hs, Hs,
+                                                  3, osz, osz, osz, osz, 0, 0, drec.data_ptr(), Br, c_mean, c_std,
+                                                  xr.data_ptr(), L.GS_BF16, L.GS_LAYOUT_NHWC, lr_.data_ptr(), st))
+
+            def composed():
+                for i, (idx, flip, top, left, h, w) in enumerate(box):
+                    o = torch.nn.functional.interpolate(
+                        ds.images[idx, top:top + h, left:left + w].permute(2, 0, 1)[None].float(), size=(osz, osz),
+                        mode="bilinear", align_corners=False, antialias=False)
+                    tmp[i] = o[0].flip(-1) if flip else o[0]
+                return ((tmp - t_mean) / t_std).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+
+            c_ms = timeit(composed, 5, warmup=1)
+            k_ms = timeit(lambda: cb.copy_(ca), 50)
+            f_ms = timeit(fused, 50)  # HIP events around each launch, the median of 50; timed last: rec() batches it
+            rec("resample", alg, *f_ms, "libgsync", B=Br, geometry=f"{Hs}x{Hs}x3 -> {osz}x{osz}", out="bf16 nhwc normalised",
+                copy_median_ms=k_ms[0], copy_avg_ms=k_ms[1], copy_GBps=alg / (k_ms[0] * 1e-3) / 1e9,
+                median_GBps=alg / (f_ms[0] * 1e-3) / 1e9, frac_of_copy=k_ms[0] / f_ms[0],
+                torch_median_ms=c_ms[0], torch_avg_ms=c_ms[1], ratio_to_torch=f_ms[0] / c_ms[0])
+            del ds, ca, cb, tmp
     if not args.skip_torch and want("lamb"):
         # a LAMB step of the same arithmetic as torch foreach ops, everything on the device
         bp, bm, bv = [p.clone() for p in params], [x.clone() for x in ms], [x.clone() for x in vs]

@@ -14,6 +14,9 @@ Public surface:
                             in the logits' dtype), optionally advancing a Metrics on the device
   MixUpCutMix / MixedTarget  MixUp and CutMix inside the device input kernel (data.DeviceDataLoader(mix=...))
                             and the pair targets the criterion takes in place of labels
+  RandomResizedCropFlip / ResizeCenterCrop  the resize-based input transforms (RandomResizedCrop + flip, or
+                            Resize + CenterCrop, + ToTensor + Normalize) as one launch per batch
+                            (data.DeviceDataLoader(transform=...))
   compat.deepspeed / compat.colossalai  API shims for the other two trainers
 """
 from . import _lib  # noqa: F401
@@ -21,7 +24,7 @@ from .comm import Communicator, destroy_communicators, get_communicator  # noqa:
 from .ddp import DDP, DistributedDataParallel, GradBucket, compute_bucket_assignment_by_size  # noqa: F401
 from .graphs import CapturedStep  # noqa: F401
 from .ema import AveragedModel, ShardedAveragedModel, get_ema_multi_avg_fn, get_swa_multi_avg_fn  # noqa: F401
-from .data import MixedTarget, MixUpCutMix  # noqa: F401
+from .data import MixedTarget, MixUpCutMix, RandomResizedCropFlip, ResizeCenterCrop  # noqa: F401
 from .evaluation import Metrics, evaluate  # noqa: F401
 from .loss import CrossEntropyLoss, cross_entropy  # noqa: F401
 from .flatten import copy_flat_to, flatten_dense_tensors, unflatten_dense_tensors  # noqa: F401

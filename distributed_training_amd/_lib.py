@@ -122,6 +122,8 @@ SIGNATURES = {
                                   _vp, _c_i64, _vp, _c_int, _c_int, _vp, _vp]),
     "gs_image_augment_mix": (_c_int, [_c_int, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                       _vp, _vp, _c_i64, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "gs_image_resample": (_c_int, [_c_int, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                   _c_int, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp]),
     "gs_bn_bwd_partials": (_c_int, [_c_i64, _c_int]),
     "gs_bn_bwd_reduce": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _vp]),
     "gs_bn_bwd_reduce_fork": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _vp]),

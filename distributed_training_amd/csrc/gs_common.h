@@ -270,6 +270,105 @@ GS_HD inline float mix_pixel(float a, float b, const MixRec& r, int y, int x) {
 }
 int hip_image_augment_mix(int device, const ImageMixAugArgs& a, void* stream);
 
+// gs_image_resample: bilinear resized crop of a per-sample box (+ hflip, ToTensor, Normalize, bf16 cast).
+struct ImageResampleArgs {
+  const uint8_t* src;     // [n_src, H, W, C] uint8
+  const int64_t* labels;  // [n_src] or NULL
+  int64_t n_src;
+  int H, W, C, out_h, out_w;
+  int virt_h, virt_w, off_y, off_x;  // the virtual output frame: d_y = y + off_y, d_x = x' + off_x
+  const int32_t* rec;     // [B, 4] = (sample index, flip, top | left << 16, h | w << 16)
+  int64_t B;
+  void* out;              // [B, C, out_h, out_w] (NCHW) or [B, out_h, out_w, C] (NHWC)
+  int out_dtype, layout;
+  int64_t* out_labels;    // [B] or NULL
+  int normalize;          // (o - mean[c]) / std[c] follows the blend (C <= 4)
+  float mean[4], std[4];
+};
+// A sample's record as both backends read it.  The host backend has rejected what is invalid; the
+// device cannot, so here an index outside the set clears ok (zeros and label 0) and the box is
+// clamped into the image: top <= H - 1, left <= W - 1, 1 <= h <= H - top, 1 <= w <= W - left.
+struct ResampleBox {
+  int idx, flip, top, left, h, w;
+  bool ok;
+};
+GS_HD inline ResampleBox resample_decode(int32_t w0, int32_t w1, int32_t w2, int32_t w3, int64_t n_src, int H,
+                                         int W) {
+  ResampleBox r;
+  r.ok = w0 >= 0 && w0 < n_src;
+  r.idx = r.ok ? w0 : 0;
+  r.flip = w1 != 0;
+  const uint32_t tl = static_cast<uint32_t>(w2), hw = static_cast<uint32_t>(w3);
+  const int top = static_cast<int>(tl & 0xffffu), left = static_cast<int>(tl >> 16);
+  const int h = static_cast<int>(hw & 0xffffu), w = static_cast<int>(hw >> 16);
+  r.top = top < H - 1 ? top : H - 1;
+  r.left = left < W - 1 ? left : W - 1;
+  r.h = h < 1 ? 1 : (h < H - r.top ? h : H - r.top);
+  r.w = w < 1 ? 1 : (w < W - r.left ? w : W - r.left);
+  return r;
+}
+// The two taps and weights of output coordinate d along an axis whose box extent is n, with
+// scale = resample_scale(n, V) for the virtual output extent V (torch's bilinear,
+// align_corners=False, antialias=False): every operation rounded once in fp32, no fma.
+struct ResampleTap {
+  int i0, i1;
+  float l0, l1;
+};
+GS_HD inline float resample_scale(int n, int V) { return static_cast<float>(n) / static_cast<float>(V); }
+GS_HD inline ResampleTap resample_tap(int d, float scale, int n) {
+  ResampleTap t;
+  float s = (static_cast<float>(d) + 0.5f) * scale - 0.5f;
+  s = s > 0.f ? s : 0.f;
+  const int i = static_cast<int>(s);
+  t.i0 = i < n - 1 ? i : n - 1;
+  t.i1 = t.i0 + 1 < n - 1 ? t.i0 + 1 : n - 1;
+  t.l1 = s - static_cast<float>(t.i0);
+  t.l0 = 1.f - t.l1;
+  return t;
+}
+// float(u8) / 255.f without the division: the product with fl(1 / 255) and one Newton correction
+// (the remainder is exact in the fma).  Equal to the IEEE quotient, bit for bit, for all 256 bytes;
+// the host backend keeps a table of true quotients, which the tests compare the device against.
+GS_HD inline float resample_unit(uint8_t v) {
+  const float x = static_cast<float>(v), r = 1.f / 255.f;
+  const float q = x * r;
+  return fmaf(fmaf(-q, 255.f, x), r, q);
+}
+// One output value from the four taps' quotients u8 / 255.f (p00 p01 on row i0, p10 p11 on row i1)
+GS_HD inline float resample_blend(float p00, float p01, float p10, float p11, const ResampleTap& ty,
+                                  const ResampleTap& tx) {
+  const float t = p00 * tx.l0 + p01 * tx.l1;
+  const float u = p10 * tx.l0 + p11 * tx.l1;
+  return t * ty.l0 + u * ty.l1;
+}
+GS_HD inline float resample_norm(float o, float mean, float std) { return (o - mean) / std; }
+// output element k of a sample -> (c, y, x) in the layout's order
+GS_HD inline void resample_cyx(int layout, int64_t k, int C, int out_h, int out_w, int* c, int* y, int* x) {
+  if (layout == GS_LAYOUT_NCHW) {
+    *x = static_cast<int>(k % out_w);
+    *y = static_cast<int>((k / out_w) % out_h);
+    *c = static_cast<int>(k / (static_cast<int64_t>(out_w) * out_h));
+  } else {
+    *c = static_cast<int>(k % C);
+    *x = static_cast<int>((k / C) % out_w);
+    *y = static_cast<int>(k / (static_cast<int64_t>(C) * out_w));
+  }
+}
+// One output element (c, y, x) of a decoded sample, its taps read from the image set through
+// tab[u8] = float(u8) / 255.f (the quotients' bits, without four divisions per output)
+GS_HD inline float resample_pixel(const ImageResampleArgs& a, const ResampleBox& r, float scale_y, float scale_x,
+                                  const float* tab, int c, int y, int x) {
+  const ResampleTap ty = resample_tap(y + a.off_y, scale_y, r.h);
+  const ResampleTap tx = resample_tap((r.flip ? a.out_w - 1 - x : x) + a.off_x, scale_x, r.w);
+  const uint8_t* img = a.src + static_cast<int64_t>(r.idx) * a.H * a.W * a.C;
+  const uint8_t* r0 = img + (static_cast<int64_t>(r.top + ty.i0) * a.W + r.left) * a.C + c;
+  const uint8_t* r1 = img + (static_cast<int64_t>(r.top + ty.i1) * a.W + r.left) * a.C + c;
+  const float o = resample_blend(tab[r0[tx.i0 * a.C]], tab[r0[tx.i1 * a.C]], tab[r1[tx.i0 * a.C]],
+                                 tab[r1[tx.i1 * a.C]], ty, tx);
+  return a.normalize ? resample_norm(o, a.mean[c], a.std[c]) : o;
+}
+int hip_image_resample(int device, const ImageResampleArgs& a, void* stream);
+
 // Adam's step-varying hyper-parameters from a device step counter (torch's
 // capturable=True): step += 1 unless found_inf; then, in double as the host
 // path forms them, hyper = [-(lr/bc1), sqrt(bc2), 1 - lr*wd] rounded to fp32.

@@ -136,6 +136,37 @@ int host_image_augment(const ImageAugArgs& a, const ImageMixAugArgs* mx = nullpt
   return GS_OK;
 }
 
+// tab[u8] = float(u8) / 255.f, the taps of gs_image_resample
+const float* resample_table() {
+  static const struct Table {
+    float v[256];
+    Table() {
+      for (int i = 0; i < 256; ++i) v[i] = static_cast<float>(i) / 255.f;
+    }
+  } t;
+  return t.v;
+}
+
+int host_image_resample(const ImageResampleArgs& a) {
+  const int64_t per = static_cast<int64_t>(a.C) * a.out_h * a.out_w;
+  const float* tab = resample_table();
+  for (int64_t b = 0; b < a.B; ++b) {
+    const int32_t* w = a.rec + 4 * b;
+    const ResampleBox r = resample_decode(w[0], w[1], w[2], w[3], a.n_src, a.H, a.W);
+    if (a.out_labels) a.out_labels[b] = a.labels ? a.labels[r.idx] : 0;
+    const float sy = resample_scale(r.h, a.virt_h), sx = resample_scale(r.w, a.virt_w);
+    for (int64_t k = 0; k < per; ++k) {
+      int c, y, x;
+      resample_cyx(a.layout, k, a.C, a.out_h, a.out_w, &c, &y, &x);
+      const float v = resample_pixel(a, r, sy, sx, tab, c, y, x);
+      const int64_t o = b * per + k;
+      if (a.out_dtype == GS_F32) static_cast<float*>(a.out)[o] = v;
+      else static_cast<uint16_t*>(a.out)[o] = f32_to_bf16(v);
+    }
+  }
+  return GS_OK;
+}
+
 }  // namespace
 }  // namespace gs
 
@@ -306,6 +337,53 @@ int gs_image_augment_mix(int device_kind, int device, const uint8_t* src, const 
   }
   if (hip_device_count() <= device) return fail(GS_ENODEV, w + ": HIP device not available");
   return hip_image_augment_mix(device, a, stream);
+}
+
+int gs_image_resample(int device_kind, int device, const uint8_t* src, const int64_t* labels, int64_t n_src,
+                      int H, int W, int C, int out_h, int out_w, int virt_h, int virt_w, int off_y, int off_x,
+                      const int32_t* rec, int64_t B, const float* mean, const float* std, void* out,
+                      int out_dtype, int out_layout, int64_t* out_labels, void* stream) {
+  const std::string w("gs_image_resample");
+  GS_CHECK_ARG(device_kind == GS_DEV_HOST || device_kind == GS_DEV_HIP, w + ": bad device_kind");
+  GS_CHECK_ARG(B >= 0 && n_src >= 0 && H > 0 && W > 0 && C > 0 && out_h > 0 && out_w > 0, w + ": bad geometry");
+  GS_CHECK_ARG(H <= 0xffff && W <= 0xffff && out_h <= 0xffff && out_w <= 0xffff,
+               w + ": an extent does not fit its 16-bit field");
+  GS_CHECK_ARG(n_src <= INT32_MAX, w + ": an index does not fit its field");
+  GS_CHECK_ARG(virt_h > 0 && virt_w > 0 && virt_h <= 0xffff && virt_w <= 0xffff && off_y >= 0 && off_x >= 0 &&
+                   off_y + out_h <= virt_h && off_x + out_w <= virt_w,
+               w + ": the crop lies outside the virtual output frame");
+  GS_CHECK_ARG(out_dtype == GS_F32 || out_dtype == GS_BF16, w + ": out dtype must be f32 or bf16");
+  GS_CHECK_ARG(out_layout == GS_LAYOUT_NCHW || out_layout == GS_LAYOUT_NHWC, w + ": bad layout");
+  GS_CHECK_ARG((mean == nullptr) == (std == nullptr), w + ": mean and std go together");
+  GS_CHECK_ARG(mean == nullptr || C <= 4, w + ": mean / std take at most 4 channels");
+  ImageResampleArgs a{};
+  a.src = src; a.labels = labels; a.n_src = n_src;
+  a.H = H; a.W = W; a.C = C; a.out_h = out_h; a.out_w = out_w;
+  a.virt_h = virt_h; a.virt_w = virt_w; a.off_y = off_y; a.off_x = off_x;
+  a.rec = rec; a.B = B; a.out = out; a.out_dtype = out_dtype; a.layout = out_layout; a.out_labels = out_labels;
+  a.normalize = mean != nullptr;
+  for (int c = 0; c < 4; ++c) {
+    a.mean[c] = (mean && c < C) ? mean[c] : 0.f;
+    a.std[c] = (std && c < C) ? std[c] : 1.f;
+    GS_CHECK_ARG(a.std[c] != 0.f, w + ": std is 0");
+  }
+  if (B == 0) return GS_OK;
+  GS_CHECK_ARG(src && rec && out, w + ": NULL buffer");
+  if (device_kind == GS_DEV_HOST) {
+    for (int64_t b = 0; b < B; ++b) {
+      const int32_t* p = rec + 4 * b;
+      const uint32_t tl = static_cast<uint32_t>(p[2]), hw = static_cast<uint32_t>(p[3]);
+      const int top = static_cast<int>(tl & 0xffffu), left = static_cast<int>(tl >> 16);
+      const int h = static_cast<int>(hw & 0xffffu), bw = static_cast<int>(hw >> 16);
+      GS_CHECK_ARG(p[0] >= 0 && p[0] < n_src, w + ": sample index out of range");
+      GS_CHECK_ARG(h > 0 && bw > 0, w + ": empty box");
+      GS_CHECK_ARG(top + h <= H && left + bw <= W, w + ": box outside the image");
+    }
+    return host_image_resample(a);
+  }
+  GS_CHECK_ARG((reinterpret_cast<uintptr_t>(rec) & 15u) == 0, w + ": rec must be 16-byte aligned");
+  if (hip_device_count() <= device) return fail(GS_ENODEV, w + ": HIP device not available");
+  return hip_image_resample(device, a, stream);
 }
 
 }  // extern "C"

@@ -28,6 +28,11 @@ Parity with the reference pipeline is exact, not statistical:
   augmentations as with the reference's DataLoader, and the generator is left
   in the same state.
 
+Image sets of another shape (pre-resized 256x256, downsampled ImageNet 64x64)
+take the resize-based transforms :class:`RandomResizedCropFlip` and
+:class:`ResizeCenterCrop` (+ ``Normalize``): one ``gs_image_resample`` launch
+per batch, boxes drawn from the transform's own numpy generator.
+
 There is no dataset download (no network): :meth:`ImageDataset.cifar10_bin`
 reads the CIFAR-10 *binary* distribution from disk when present;
 :meth:`ImageDataset.synthetic` makes a seeded stand-in of the same shape.
@@ -302,6 +307,168 @@ class MixUpCutMix:
         return rec
 
 
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, (int, np.integer)) else (int(v[0]), int(v[1]))
+
+
+def _mean_std(mean, std, what):
+    if (mean is None) != (std is None):
+        raise ValueError(f"{what}: mean and std go together")
+    if mean is None:
+        return None, None
+    mean, std = tuple(float(m) for m in mean), tuple(float(s) for s in std)
+    if len(mean) != len(std) or not 1 <= len(mean) <= 4:
+        raise ValueError(f"{what}: mean and std must have the same length, at most 4")
+    if any(np.float32(s) == 0 for s in std):
+        raise ValueError(f"{what}: std must not be 0")
+    return mean, std
+
+
+def _pack_records(idx, flip, top, left, h, w) -> np.ndarray:
+    """the ``[B, 4]`` int32 records of ``gs_image_resample``: (index, flip, top | left << 16, h | w << 16)"""
+    rec = np.empty((len(idx), 4), dtype=np.int32)
+    rec[:, 0] = idx
+    rec[:, 1] = flip
+    rec[:, 2] = (np.asarray(top, dtype=np.int64) | (np.asarray(left, dtype=np.int64) << 16)).astype(np.uint32).view(np.int32)
+    rec[:, 3] = (np.asarray(h, dtype=np.int64) | (np.asarray(w, dtype=np.int64) << 16)).astype(np.uint32).view(np.int32)
+    return rec
+
+
+class RandomResizedCropFlip:
+    """Compose([RandomResizedCrop(size, scale, ratio, antialias=False), RandomHorizontalFlip(), ToTensor(),
+    Normalize(mean, std)]) of torchvision's tensor path for :class:`DeviceDataLoader`: it draws, per batch, the
+    ``[B, 4]`` int32 records ``gs_image_resample`` (include/gsync.h) applies in one launch:
+    ``(index, flip, top | left << 16, h | w << 16)``.  ``flip=False`` leaves every image unflipped;
+    ``mean=None, std=None`` leaves out ``Normalize``.
+
+    The draws come from this object's own ``numpy.random.Generator`` (PCG64 seeded ``[seed, rank]``;
+    ``rank=None``: the process group's rank if one is initialised, else 0), never from torch's generators.
+    ``state_dict()`` / ``load_state_dict()`` carry the bit generator's state.
+
+    Draw order per batch of ``B`` samples of ``H x W`` images; the count is fixed, so the stream's state does not
+    depend on the data:
+
+    1. ``u = rng.random((B, 10, 2))``: ten tries per sample
+    2. ``f = rng.random(B)``
+    3. ``pos = rng.random((B, 2))``
+
+    Try ``k`` of a sample follows torchvision's ``get_params`` in numpy float64 operations:
+    ``area = H * W * (s0 + u[k, 0] * (s1 - s0))``,
+    ``r = np.exp(np.log(r0) + u[k, 1] * (np.log(r1) - np.log(r0)))``, ``w = np.rint(np.sqrt(area * r))``,
+    ``h = np.rint(np.sqrt(area / r))``; the try is valid when ``0 < w <= W`` and ``0 < h <= H``, and the first
+    valid try wins.  Then ``top = floor(pos[0] * (H - h + 1))`` and ``left = floor(pos[1] * (W - w + 1))``.
+    A sample with no valid try takes torchvision's ratio-clamped central crop and ignores ``pos``: with
+    ``in_ratio = W / H``, ``w = W, h = int(round(W / min(ratio)))`` if ``in_ratio < min(ratio)``;
+    ``h = H, w = int(round(H * max(ratio)))`` if ``in_ratio > max(ratio)``; else the whole image; h and w are
+    kept in ``[1, H]`` and ``[1, W]``; ``top = (H - h) // 2``, ``left = (W - w) // 2``.
+    ``flip = f < 0.5`` (0 when ``flip=False``; ``f`` is drawn all the same)."""
+
+    def __init__(self, size, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip: bool = True, mean=None, std=None,
+                 seed: int = 0, rank: int | None = None):
+        self.size = _pair(size)
+        if min(self.size) <= 0 or max(self.size) > 65535:
+            raise ValueError("RandomResizedCropFlip: size must be in [1, 65535]")
+        self.scale, self.ratio = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
+        if not (0 < self.scale[0] <= self.scale[1]) or not (0 < self.ratio[0] <= self.ratio[1]):
+            raise ValueError("RandomResizedCropFlip: scale and ratio must be positive (min, max) pairs")
+        self.flip = bool(flip)
+        self.mean, self.std = _mean_std(mean, std, "RandomResizedCropFlip")
+        if rank is None:
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.seed, self.rank = int(seed), int(rank)
+        self.rng = np.random.Generator(np.random.PCG64([self.seed, self.rank]))
+
+    def state_dict(self) -> dict:
+        return {"bit_generator": self.rng.bit_generator.state}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.rng.bit_generator.state = state["bit_generator"]
+
+    def out_hw(self, H, W):
+        return self.size
+
+    def frame(self, H, W):
+        """(virt_h, virt_w, off_y, off_x): the output is the whole resized box"""
+        return self.size[0], self.size[1], 0, 0
+
+    def records(self, idx: np.ndarray, H: int, W: int) -> np.ndarray:
+        """the next batch's ``[B, 4]`` int32 records (see the class's docstring for the draws)"""
+        rng = self.rng
+        B = len(idx)
+        u = rng.random((B, 10, 2))
+        f = rng.random(B)
+        pos = rng.random((B, 2))
+        (s0, s1), (r0, r1) = self.scale, self.ratio
+        area = (H * W) * (s0 + u[:, :, 0] * (s1 - s0))
+        lr0, lr1 = np.log(r0), np.log(r1)
+        r = np.exp(lr0 + u[:, :, 1] * (lr1 - lr0))
+        w = np.rint(np.sqrt(area * r))
+        h = np.rint(np.sqrt(area / r))
+        valid = (w > 0) & (w <= W) & (h > 0) & (h <= H)
+        any_valid = valid.any(axis=1)
+        first = np.argmax(valid, axis=1)
+        rows = np.arange(B)
+        w = w[rows, first].astype(np.int64)
+        h = h[rows, first].astype(np.int64)
+        top = np.floor(pos[:, 0] * (H - h + 1)).astype(np.int64)
+        left = np.floor(pos[:, 1] * (W - w + 1)).astype(np.int64)
+        if not any_valid.all():
+            in_ratio = float(W) / float(H)
+            if in_ratio < min(self.ratio):
+                fw, fh = W, int(round(W / min(self.ratio)))
+            elif in_ratio > max(self.ratio):
+                fh, fw = H, int(round(H * max(self.ratio)))
+            else:
+                fw, fh = W, H
+            fh, fw = min(max(fh, 1), H), min(max(fw, 1), W)
+            h, w = np.where(any_valid, h, fh), np.where(any_valid, w, fw)
+            top, left = np.where(any_valid, top, (H - fh) // 2), np.where(any_valid, left, (W - fw) // 2)
+        flip = (f < 0.5) if self.flip else np.zeros(B, dtype=bool)
+        return _pack_records(idx, flip, top, left, h, w)
+
+
+class ResizeCenterCrop:
+    """Compose([Resize(resize, antialias=False), CenterCrop(crop), ToTensor(), Normalize(mean, std)]) of
+    torchvision's tensor path for :class:`DeviceDataLoader`; deterministic.  An int ``resize`` makes the image's
+    shorter side ``resize`` and the longer one ``int(resize * long / short)``; a pair is ``(h, w)``; ``None``
+    keeps the image's extent.  ``crop`` (an int or ``(h, w)``; ``None``: the whole resized image) is taken at
+    ``int(round((V - c) / 2.0))`` of the resized extent ``V`` on each axis and must fit inside it.
+
+    The kernel never forms the resized image: the record's box is the whole image, and the launch's virtual
+    output frame is the resized extent with the crop's offset, which equals resizing and then slicing exactly.
+    ``resize=None, crop=None`` is ``ToTensor()`` (+ ``Normalize``) alone, bit-identical to ``(x / 255 - mean) / std``
+    (every second weight is 0): with ``mean = std = (0.5, 0.5, 0.5)`` the DeepSpeed reference's transform
+    (R:resnet/deepspeed/deepspeed_train.py:227-230)."""
+
+    def __init__(self, resize=None, crop=None, mean=None, std=None):
+        self.resize = None if resize is None else (int(resize) if isinstance(resize, (int, np.integer)) else _pair(resize))
+        self.crop = None if crop is None else _pair(crop)
+        self.mean, self.std = _mean_std(mean, std, "ResizeCenterCrop")
+
+    def _virt(self, H, W):
+        if self.resize is None:
+            return H, W
+        if isinstance(self.resize, int):
+            s = self.resize
+            return (s, int(s * W / H)) if H <= W else (int(s * H / W), s)
+        return self.resize
+
+    def out_hw(self, H, W):
+        return self.frame(H, W)[4]
+
+    def frame(self, H, W):
+        """(virt_h, virt_w, off_y, off_x, (out_h, out_w))"""
+        vh, vw = self._virt(H, W)
+        ch, cw = self.crop if self.crop is not None else (vh, vw)
+        if not (0 < ch <= vh <= 65535 and 0 < cw <= vw <= 65535):
+            raise ValueError(f"ResizeCenterCrop: crop {ch}x{cw} does not fit the resized image {vh}x{vw}")
+        return vh, vw, int(round((vh - ch) / 2.0)), int(round((vw - cw) / 2.0)), (ch, cw)
+
+    def records(self, idx: np.ndarray, H: int, W: int) -> np.ndarray:
+        z = np.zeros(len(idx), dtype=np.int64)
+        return _pack_records(idx, z, z, z, z + H, z + W)
+
+
 class DeviceDataLoader:
     """``DataLoader(dataset, batch_size, shuffle=False, sampler=..., drop_last=...)``
     over an :class:`ImageDataset`, yielding ``(images, labels)`` on the
@@ -309,10 +476,14 @@ class DeviceDataLoader:
     ``memory_format``, labels int64 ``[B]``.
 
     ``mix``: a :class:`MixUpCutMix`; the batch is then mixed inside the same kernel
-    (``gs_image_augment_mix``) and the loader yields ``(images, MixedTarget)``."""
+    (``gs_image_augment_mix``) and the loader yields ``(images, MixedTarget)``.
+
+    ``transform``: a :class:`PadFlipCrop` (``gs_image_augment``), or a :class:`RandomResizedCropFlip` or
+    :class:`ResizeCenterCrop` (``gs_image_resample``: resized crop, flip, ToTensor and Normalize in one launch).
+    The latter two draw nothing from torch's generators and cannot be combined with ``mix`` yet."""
 
     def __init__(self, dataset: ImageDataset, batch_size: int = 1, shuffle: bool = False, sampler=None,
-                 drop_last: bool = False, transform: PadFlipCrop = TEST_TRANSFORM,
+                 drop_last: bool = False, transform=TEST_TRANSFORM,
                  out_dtype: torch.dtype = torch.float32, memory_format=torch.contiguous_format,
                  generator: torch.Generator | None = None, mix: MixUpCutMix | None = None):
         if shuffle and sampler is not None:
@@ -335,6 +506,14 @@ class DeviceDataLoader:
         self._kind = L.GS_DEV_HIP if self.device.type == "cuda" else L.GS_DEV_HOST
         if self._kind == L.GS_DEV_HIP and not L.available():
             raise L.GsyncUnavailable(L._load_error)
+        self._resample = isinstance(transform, (RandomResizedCropFlip, ResizeCenterCrop))
+        if self._resample and mix is not None:
+            raise NotImplementedError("mix= with RandomResizedCropFlip / ResizeCenterCrop: mixing two resized crops "
+                                      "in one launch is not implemented; use a PadFlipCrop transform with mix=")
+        if self._resample and max(dataset.H, dataset.W) > 65535:
+            raise ValueError("gs_image_resample takes images of at most 65535 x 65535")
+        if self._resample and transform.mean is not None and len(transform.mean) != dataset.C:
+            raise ValueError(f"transform has {len(transform.mean)} mean / std values for {dataset.C} channels")
         self.oh, self.ow = transform.out_hw(dataset.H, dataset.W)
 
     def _indices(self) -> list:
@@ -373,10 +552,40 @@ class DeviceDataLoader:
         self._rng_set(st)
         return params
 
+    def _iter_resample(self, order: np.ndarray):
+        """the batches of a RandomResizedCropFlip / ResizeCenterCrop loader: one gs_image_resample each"""
+        t, ds, bs = self.transform, self.dataset, self.batch_size
+        vh, vw, oy, ox = t.frame(ds.H, ds.W)[:4]
+        hip = self._kind == L.GS_DEV_HIP
+        mean = std = None
+        if t.mean is not None:
+            mean, std = (ctypes.c_float * ds.C)(*t.mean), (ctypes.c_float * ds.C)(*t.std)
+        for k in range(len(self)):
+            idx = order[k * bs:(k + 1) * bs]
+            B = idx.size
+            # the records travel as PadFlipCrop's params do: a pinned block per batch, a non-blocking copy
+            rec = torch.empty((B, 4), dtype=torch.int32, pin_memory=hip)
+            rec.numpy()[...] = t.records(idx, ds.H, ds.W)
+            drec = rec.to(self.device, non_blocking=True) if hip else rec
+            out = torch.empty((B, ds.C, self.oh, self.ow), dtype=self.out_dtype, device=self.device,
+                              memory_format=self.memory_format)
+            layout = L.GS_LAYOUT_NHWC if (self.memory_format == torch.channels_last and B > 0) else L.GS_LAYOUT_NCHW
+            labels = torch.empty(B, dtype=torch.int64, device=self.device)
+            L.check(L.lib().gs_image_resample(self._kind, self.device.index or 0, ds.images.data_ptr(),
+                                               ds.labels.data_ptr(), ds.n, ds.H, ds.W, ds.C, self.oh, self.ow, vh, vw,
+                                               oy, ox, drec.data_ptr(), B, mean, std, out.data_ptr(),
+                                               L.gs_dtype(self.out_dtype), layout, labels.data_ptr(),
+                                               L.stream_ptr(self.device)),
+                    "gs_image_resample")
+            yield out, labels
+
     def __iter__(self):
         order = np.asarray(self._indices(), dtype=np.int64)
         if order.size and (order.min() < 0 or order.max() >= len(self.dataset)):
             raise IndexError("sampler produced an index outside the dataset")
+        if self._resample:
+            yield from self._iter_resample(order)
+            return
         # _BaseDataLoaderIter.__init__: one int64 draw for the workers' base seed
         torch.empty((), dtype=torch.int64).random_(generator=self.generator)
         bs = self.batch_size

@@ -730,6 +730,39 @@ int gs_image_augment_mix(int device_kind, int device, const uint8_t* src, const 
                          int H, int W, int C, int pad, int out_h, int out_w, const int32_t* params,
                          const int32_t* mix, int64_t B, void* out, int out_dtype, int out_layout,
                          int64_t* out_labels, int64_t* out_labels_b, float* out_lam, void* stream);
+/* The resize-based input step in one launch: gather + bilinear resized crop of a per-sample box +
+ * hflip + ToTensor (+ Normalize) (+ bf16 cast), labels gathered alongside.
+ * replaces: torchvision RandomResizedCrop / Resize + CenterCrop / RandomHorizontalFlip / ToTensor /
+ *           Normalize on tensors, i.e. F.interpolate(x / 255, mode="bilinear", align_corners=False,
+ *           antialias=False) of each sample's box, flipped and normalised.
+ * rec: [B, 4] int32, one record per batch position: (index, flip, top | left << 16, h | w << 16),
+ * the box [top, top + h) x [left, left + w) of image `index`; H, W, out_h, out_w <= 65535.
+ * (virt_h, virt_w) and (off_y, off_x) are the launch's virtual output frame: output (y, x) is
+ * coordinate d_y = y + off_y, d_x = x' + off_x of a virt_h x virt_w resize of the box, where
+ * x' = out_w - 1 - x with flip set, else x.  Training: virt = out, off = 0.  Resize(S) +
+ * CenterCrop(c): the whole image as the box, virt = the resized extent, off = the crop's offset.
+ * Along an axis with box extent n and virtual extent V, every operation rounded once in fp32, no fma:
+ *   scale = float(n) / float(V)
+ *   s  = max((float(d) + 0.5f) * scale - 0.5f, 0.f)
+ *   i0 = min(int(s), n - 1);  i1 = min(i0 + 1, n - 1);  l1 = s - float(i0);  l0 = 1.f - l1
+ * With the taps p = float(u8) / 255.f at (y.i0, x.i0), (y.i0, x.i1), (y.i1, x.i0), (y.i1, x.i1) = a, b, c, d:
+ *   t = a * x.l0 + b * x.l1;  u = c * x.l0 + d * x.l1;  o = t * y.l0 + u * y.l1
+ * then, if mean and std are given (host arrays of C floats, C <= 4; both or neither),
+ * (o - mean[c]) / std[c], then the bf16 cast (round to nearest even).
+ * GS_DEV_HOST rejects with GS_EINVAL, before writing anything: an index outside the set, an empty
+ * box, a box outside the image, std[c] == 0, and a frame with off < 0 or off + out > virt.
+ * GS_DEV_HIP checks the launch-uniform arguments the same way but cannot read the records on the
+ * host: an index outside the set writes zeros and label 0, a box is clamped into the image
+ * (top <= H - 1, left <= W - 1, 1 <= h <= H - top, 1 <= w <= W - left), and nothing outside the
+ * image set is read; rec is 16-byte aligned.  One launch on `stream`, no temporaries: one workgroup
+ * per (sample, band of output rows) stages the band's source rows in LDS; a global-gather kernel
+ * with the same arithmetic when a one-row band does not fit 48 KiB, C * out_h * out_w is not a
+ * multiple of 4 (NCHW: out_h * out_w), out is not 16-byte aligned, or H > 2 * virt_h or
+ * W > 2 * virt_w (the taps skip most of the rows a band would stage). */
+int gs_image_resample(int device_kind, int device, const uint8_t* src, const int64_t* labels, int64_t n_src,
+                      int H, int W, int C, int out_h, int out_w, int virt_h, int virt_w, int off_y, int off_x,
+                      const int32_t* rec, int64_t B, const float* mean, const float* std, void* out,
+                      int out_dtype, int out_layout, int64_t* out_labels, void* stream);
 
 /* ======================================================================
  * NHWC BatchNorm backward fused with the ReLU mask and the residual add
