@@ -505,6 +505,54 @@ def main():
         rec("adam", 28 * n, *timeit(adam.step, args.iters), "torch.optim.Adam foreach")
         fadam = torch.optim.Adam(ps, lr=1e-6, fused=True)
         rec("adam", 28 * n, *timeit(fadam.step, args.iters), "torch.optim.Adam fused")
+    if want("muon"):
+        muon_row(args, dev, shapes)
+
+
+BF16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X dense bf16 matrix peak (AMD's data sheet: 2.5 PFLOP/s)
+
+
+def muon_row(args, dev, shapes, ns_steps=5, repeats=5):
+    """FusedMuon against torch.optim.Muon on the model's matrix-shaped weights (conv
+    filters and fc; the filters reshaped 2-D for torch): both in this process, alternating,
+    each repeat `iters` steps between one pair of device events after a warm-up and a
+    synchronise.  One JSON line: ms per step of both (median over the repeats, and every
+    repeat), the launch counts (fused: the kernels step() enqueues; torch: 7 + 3 * ns_steps
+    per parameter, its op sequence) and the achieved bf16 FLOP/s of the Newton-Schulz part,
+    Σ 2m²n + 2m³ + 2m²n per tensor and iteration."""
+    from distributed_training_amd.optim import FusedMuon
+
+    mats = [(s[0], torch.Size(s).numel() // s[0]) for s in shapes if len(s) in (2, 4)]
+    g = torch.Generator(device=dev).manual_seed(1)
+    mine = [torch.nn.Parameter(torch.randn(a, b, device=dev, generator=g)) for a, b in mats]
+    theirs = [torch.nn.Parameter(p.detach().clone()) for p in mine]
+    for p, q in zip(mine, theirs):
+        p.grad = torch.randn(p.shape, device=dev, generator=g) * 0.01
+        q.grad = p.grad.clone()
+    fused, ref = FusedMuon(mine, lr=1e-6, ns_steps=ns_steps), torch.optim.Muon(theirs, lr=1e-6, ns_steps=ns_steps)
+    flop = 0
+    for a, b in mats:
+        m, k = min(a, b), max(a, b)
+        flop += ns_steps * (4 * m * m * k + 2 * m ** 3)
+
+    def run(opt):
+        for _ in range(3):
+            opt.step()
+        torch.cuda.synchronize()
+        return timeit_batched(opt.step, args.iters)
+
+    t_f, t_t = [], []
+    for _ in range(repeats):
+        t_f.append(run(fused))
+        t_t.append(run(ref))
+    med = lambda ts: sorted(ts)[len(ts) // 2]  # noqa: E731
+    row = {"kernel": "muon_step", "model": args.model, "tensors": len(mats), "ns_steps": ns_steps, "tag": args.tag,
+           "fused_ms": med(t_f), "torch_ms": med(t_t), "fused_ms_repeats": t_f, "torch_ms_repeats": t_t,
+           "fused_launches": 3 * ns_steps + 4, "torch_launches": len(mats) * (7 + 3 * ns_steps),
+           "ns_gflop": flop / 1e9, "fused_ns_tflops": flop / (med(t_f) * 1e-3) / 1e12,
+           "fused_frac_of_bf16_peak": flop / (med(t_f) * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS,
+           "speedup": med(t_t) / med(t_f)}
+    print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":

@@ -43,6 +43,7 @@ GS_OP_PACK, GS_OP_UNPACK, GS_OP_SCALE, GS_OP_SQNORM, GS_OP_UNSCALE, GS_OP_SGD, G
 GS_OP_LARS_NORM, GS_OP_LARS = 9, 10
 GS_OP_LAMB_MOMENTS, GS_OP_LAMB = 11, 12
 GS_OP_EMA = 13
+GS_OP_MUON_PREP, GS_OP_MUON_GRAM, GS_OP_MUON_POLY, GS_OP_MUON_APPLY, GS_OP_MUON_UPDATE = 14, 15, 16, 17, 18
 GS_EMA_EMA, GS_EMA_SWA, GS_EMA_WARMUP = 0, 1, 2
 
 _TORCH_TO_GS = {
@@ -161,6 +162,12 @@ SIGNATURES = {
     ),
     "gs_plan_set_adapt": (_c_int, [_vp, _p_i32]),
     "gs_lars_norms": (_c_int, [_vp, _c_int, _vp, _vp]),
+    "gs_muon_layout": (_c_int, [_vp, _vp, _vp, _vp]),
+    "gs_muon_prep": (_c_int, [_vp, _c_int, _c_d, _c_int, _c_d, _vp, _vp, _c_i64, _vp]),
+    "gs_muon_gram": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_d, _vp]),
+    "gs_muon_poly": (_c_int, [_vp, _vp, _c_i64, _c_d, _c_d, _vp]),
+    "gs_muon_apply": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_d, _vp]),
+    "gs_muon_update": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_d, _c_d, _c_int, _vp]),
     "gs_lars_step": (_c_int, [_vp, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp, _vp]),
     "gs_lars_step_lowp": (_c_int, [_vp, _c_int, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp, _vp]),
     "gs_lamb_step_lowp": (_c_int, [_vp, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp]),

@@ -131,6 +131,30 @@ struct PlanArgs {
     default: return fail(GS_EINVAL, "unsupported low-precision dtype");  \
   }
 
+// ---- Muon (gs_muon_*: gs_muon_kernels.hip / gs_host.cpp) ----
+// The bf16 workspace of a plan's tensors: per tensor two X buffers [mp, np] (ping-pong),
+// Agram and Bpoly [mp, mp], every dimension padded with zeros to kMuonTile, so the GEMM
+// kernels carry no edge predicate.  The tensor is the row-major [A, B] matrix in memory;
+// X is [m, n] = [min, max] of the two (tr: stored transposed).
+constexpr int kMuonTile = 128;  // output tile of a GEMM workgroup (4 waves of 64 x 64)
+constexpr int kMuonEw = 64;     // tile of the prep / update passes (the LDS transpose)
+struct MuonDesc {
+  int64_t x[2], a, b;  // element offsets into the workspace
+  int32_t A, B, m, n, mp, np, tr, pad_;
+  double ratio[2];     // adjusted_lr / lr: [0] "original", [1] "match_rms_adamw"
+};
+struct MuonTask {
+  int32_t t, ti, tj, pad_;  // tensor, tile row, tile column
+};
+struct MuonTables {  // device (HIP plans) or host pointers
+  const MuonDesc* desc;
+  const MuonTask* gram;   // (tensor, upper-triangle tile of Agram), heaviest K = np first
+  const MuonTask* poly;   // the same tiles, heaviest K = mp first
+  const MuonTask* apply;  // (tensor, tile of X), heaviest K = mp first
+  const MuonTask* ew;     // (tensor, kMuonEw tile of the [A, B] matrix)
+  int32_t n_sym, n_apply, n_ew;
+};
+
 }  // namespace gs
 
 // The opaque plan (visible to every TU of the library).
@@ -187,6 +211,12 @@ struct gs_plan {
   std::vector<int32_t> adapt;
   void* d_lars = nullptr;
   int64_t lars_slots = 0;
+  // Muon (gs_muon_layout): the workspace layout and, on HIP plans, its device copy with
+  // the task tables (desc | gram | poly | apply | ew)
+  std::vector<gs::MuonDesc> muon;
+  int64_t muon_total = 0;   // workspace elements (bf16)
+  void* d_muon = nullptr;
+  gs::MuonTables muon_tab{};
   // launch timer ring (gs_plan_timer_enable)
   std::vector<void*> timer_ev;  // [2 * slots]: start, stop
   std::vector<int32_t> timer_kind;  // [slots]: GS_OP_* of the timed launch
@@ -570,6 +600,20 @@ int hip_lamb_moments(gs_plan* p, int gdt, const LambHyper& h, float* norms, cons
 int hip_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const float* fi, void* stream);
 int hip_lamb_hyper(double* step, const double* lr, double beta1, double beta2, int bias_correction,
                    const float* found_inf, float* hyper, void* stream);
+int hip_muon_moments(gs_plan* p, int gdt, const MuonHyper& h, float* norms, void* stream);
+// gs_muon_kernels.hip; task tables built by muon_build_tasks (gs_plan.cpp)
+struct MuonTaskLists {
+  std::vector<MuonTask> gram, poly, apply, ew;
+};
+int hip_muon_upload(gs_plan* p, const MuonTaskLists& l);
+int hip_muon_xwrite(gs_plan* p, int gdt, const MuonHyper& h, const float* norms, void* ws, void* stream);
+int hip_muon_syrk(gs_plan* p, void* ws, int poly, int xsel, float alpha, float beta, void* stream);
+int hip_muon_apply(gs_plan* p, void* ws, int xsel, float a, void* stream);
+int hip_muon_update(gs_plan* p, void* ws, int xsel, double lr, double wd, int adjust, void* stream);
+int host_muon_prep(gs_plan* p, int gdt, const MuonHyper& h, float* norms, void* ws);
+int host_muon_syrk(gs_plan* p, void* ws, int poly, int xsel, float alpha, float beta);
+int host_muon_apply(gs_plan* p, void* ws, int xsel, float a);
+int host_muon_update(gs_plan* p, void* ws, int xsel, double lr, double wd, int adjust);
 int hip_device_count();
 int hip_memset_async(void* dst, int value, size_t bytes, void* stream);
 int hip_stream_wait(void* waiter, void* signaler);

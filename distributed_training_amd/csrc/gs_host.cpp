@@ -463,6 +463,102 @@ int host_lamb(gs_plan* p, int ldt, const LambHyper& h, const float* norms, const
   return GS_OK;
 }
 
+// Muon on the host (include/gsync.h, gs_muon_*): the device stages restated as plain loops
+// on the same padded workspace, with the same rounding points (gs_math.h's muon_* texts).
+// A product is summed over ascending k, one fp32 add per bf16 x bf16 product — a fixed
+// order that is not the MFMA kernels', so host and device agree to the accumulation order
+// only.  Serial: the sizes that reach the host backend are test sizes.
+int host_muon_prep(gs_plan* p, int gdt, const MuonHyper& h, float* norms, void* ws) {
+  GS_TRY_RET(check_float(gdt));
+  GS_DISPATCH_FLOAT(gdt, GD, {
+    blockwise_sq_sums(p, norms, [&](int t) {
+      const void* gp = slot(p, 1, t);
+      float* bp = static_cast<float*>(slot(p, 2, t));
+      return [=](int64_t i, float& b, float& u) {
+        bp[i] = muon_buf(h, ldT<GD>(gp, i), bp[i]);
+        b = bp[i];
+        u = muon_u(h, ldT<GD>(gp, i), b);
+      };
+    });
+    uint16_t* w = static_cast<uint16_t*>(ws);
+    for (int t = 0; t < p->n; ++t) {
+      const MuonDesc& d = p->muon[t];
+      const void* gp = slot(p, 1, t);
+      const float* bp = static_cast<const float*>(slot(p, 2, t));
+      const float s = muon_scale(norms[2 * t + 1], h.eps);
+      for (int64_t r = 0; r < d.A; ++r)
+        for (int64_t c = 0; c < d.B; ++c) {
+          const int64_t e = r * d.B + c;
+          w[d.x[0] + (d.tr ? c * d.np + r : r * d.np + c)] = f32_to_bf16(muon_u(h, ldT<GD>(gp, e), bp[e]) * s);
+        }
+    }
+  });
+  return GS_OK;
+}
+
+// rows [0, rows) x k [0, K) of a bf16 matrix of pitch ld, as fp32
+static std::vector<float> muon_widen(const uint16_t* m, int64_t rows, int64_t K, int64_t ld) {
+  std::vector<float> f(static_cast<size_t>(rows * K));
+  for (int64_t r = 0; r < rows; ++r)
+    for (int64_t k = 0; k < K; ++k) f[r * K + k] = bf16_to_f32(m[r * ld + k]);
+  return f;
+}
+
+int host_muon_syrk(gs_plan* p, void* ws, int poly, int xsel, float alpha, float beta) {
+  uint16_t* w = static_cast<uint16_t*>(ws);
+  for (int t = 0; t < p->n; ++t) {
+    const MuonDesc& d = p->muon[t];
+    const int64_t K = poly ? d.mp : d.np, m = d.mp;
+    const uint16_t* X = w + (poly ? d.a : d.x[xsel]);
+    uint16_t* C = w + (poly ? d.b : d.a);
+    const std::vector<float> f = muon_widen(X, m, K, K);
+    for (int64_t i = 0; i < m; ++i)
+      for (int64_t j = i; j < m; ++j) {
+        float acc = 0.f;
+        for (int64_t k = 0; k < K; ++k) acc = acc + f[i * K + k] * f[j * K + k];
+        const float o = poly ? muon_poly_out(beta, alpha, acc, f[i * K + j]) : muon_gram_out(alpha, acc);
+        C[i * m + j] = C[j * m + i] = f32_to_bf16(o);
+      }
+  }
+  return GS_OK;
+}
+
+int host_muon_apply(gs_plan* p, void* ws, int xsel, float a) {
+  uint16_t* w = static_cast<uint16_t*>(ws);
+  for (int t = 0; t < p->n; ++t) {
+    const MuonDesc& d = p->muon[t];
+    const int64_t m = d.mp, n = d.np;
+    const std::vector<float> P = muon_widen(w + d.b, m, m, m), X = muon_widen(w + d.x[xsel], m, n, n);
+    uint16_t* Y = w + d.x[xsel ^ 1];
+    std::vector<float> acc(static_cast<size_t>(n));
+    for (int64_t i = 0; i < m; ++i) {
+      std::fill(acc.begin(), acc.end(), 0.f);
+      for (int64_t k = 0; k < m; ++k) {  // ascending k for every (i, j)
+        const float pk = P[i * m + k];
+        for (int64_t j = 0; j < n; ++j) acc[j] = acc[j] + pk * X[k * n + j];
+      }
+      for (int64_t j = 0; j < n; ++j) Y[i * n + j] = f32_to_bf16(muon_apply_out(a, acc[j], X[i * n + j]));
+    }
+  }
+  return GS_OK;
+}
+
+int host_muon_update(gs_plan* p, void* ws, int xsel, double lr, double wd, int adjust) {
+  const uint16_t* w = static_cast<const uint16_t*>(ws);
+  const float decay = static_cast<float>(1.0 - lr * wd);
+  for (int t = 0; t < p->n; ++t) {
+    const MuonDesc& d = p->muon[t];
+    float* pp = static_cast<float*>(slot(p, 0, t));
+    const float adj = static_cast<float>(lr * d.ratio[adjust]);
+    for (int64_t r = 0; r < d.A; ++r)
+      for (int64_t c = 0; c < d.B; ++c) {
+        const float o = bf16_to_f32(w[d.x[xsel] + (d.tr ? c * d.np + r : r * d.np + c)]);
+        pp[r * d.B + c] = muon_param(pp[r * d.B + c], decay, adj, o);
+      }
+  }
+  return GS_OK;
+}
+
 // A pairwise sum of terms pushed one by one: a binary counter of finished subtrees, small ones
 // folded first, so at most ceil(log2 n) roundings lie on any path, as in the device's tree
 // (gs_wave.h); its order differs from the device's.

@@ -220,6 +220,41 @@ GS_HD_INL float ema_lerp(bool high, float w, float wm1, float a, float s) {
   return high ? fmaf(wm1, s - a, s) : fmaf(w, s - a, a);
 }
 
+// ---------------------------------------------------------------- Muon
+// Muon (gs_muon_prep): w1 = float(1-momentum) formed in double.  The momentum and the
+// Nesterov look-ahead are two torch.lerp's (buf.lerp_(g, 1-mu), g.lerp(buf, mu)), each in
+// ema_lerp's form, so the buffer is torch's bit for bit.
+struct MuonHyper {
+  float w1, mu, eps;
+  int nesterov;
+};
+GS_HD_INL float muon_buf(const MuonHyper& h, float g, float b) {
+  float wm1;
+  bool high;
+  ema_form(h.w1, &wm1, &high);
+  return ema_lerp(high, h.w1, wm1, b, g);
+}
+// the update direction from the grad and the NEW buffer: the segmented pass sums its
+// square, the X pass recomputes it from the stored buffer — the same bits
+GS_HD_INL float muon_u(const MuonHyper& h, float g, float nb) {
+  if (!h.nesterov) return nb;
+  float wm1;
+  bool high;
+  ema_form(h.mu, &wm1, &high);
+  return ema_lerp(high, h.mu, wm1, g, nb);
+}
+// s = 1 / max(sqrt(Σu²), eps)
+GS_HD_INL float muon_scale(float su, float eps) {
+  const float nrm = sqrtf(su);
+  return 1.f / (nrm > eps ? nrm : eps);
+}
+// the three epilogues of the Newton-Schulz stages (acc: the fp32 sum of bf16 products)
+// and the parameter update; one fma each where torch's addmm rounds once
+GS_HD_INL float muon_gram_out(float alpha, float acc) { return alpha * acc; }
+GS_HD_INL float muon_poly_out(float b, float c, float acc, float d) { return fmaf(c, acc, b * d); }
+GS_HD_INL float muon_apply_out(float a, float acc, float x) { return fmaf(a, x, acc); }
+GS_HD_INL float muon_param(float p, float decay, float adj_lr, float o) { return p * decay - adj_lr * o; }
+
 // ---------------------------------------------------------------- gradient-norm clip
 // Gradient-norm clip folded into an update launch (gs_plan_set_clip): the
 // update's workgroups form the coefficient themselves, so no coefficient

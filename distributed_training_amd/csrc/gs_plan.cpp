@@ -670,6 +670,139 @@ int gs_lamb_hyper(int device_kind, double* step, const double* lr, double beta1,
   return hip_lamb_hyper(step, lr, beta1, beta2, bias_correction, found_inf, hyper, stream);
 }
 
+// ---- Muon: the workspace layout and the task tables of the grouped launches ----
+int gs_muon_layout(gs_plan* p, const int64_t* rows, int64_t* layout_out, int64_t* total_out) {
+  PLAN_OK(p);
+  GS_CHECK_ARG(p->n == 0 || rows != nullptr, "gs_muon_layout: NULL rows");
+  std::vector<MuonDesc> desc(p->n);
+  int64_t off = 0;
+  auto up = [](int64_t x) { return (x + kMuonTile - 1) / kMuonTile * kMuonTile; };
+  for (int t = 0; t < p->n; ++t) {
+    const int64_t A = rows[t], numel = p->numel[t];
+    if (A <= 0 || numel <= 0 || numel % A != 0 || numel > (int64_t(1) << 30))
+      return fail(GS_EINVAL, "gs_muon_layout: tensor " + std::to_string(t) + " is not an [A, B] matrix (rows " +
+                                 std::to_string(A) + ", numel " + std::to_string(numel) + ")");
+    const int64_t B = numel / A;
+    MuonDesc d{};
+    d.A = static_cast<int32_t>(A);
+    d.B = static_cast<int32_t>(B);
+    d.tr = A > B;
+    d.m = static_cast<int32_t>(std::min(A, B));
+    d.n = static_cast<int32_t>(std::max(A, B));
+    d.mp = static_cast<int32_t>(up(d.m));
+    d.np = static_cast<int32_t>(up(d.n));
+    const int64_t xs = static_cast<int64_t>(d.mp) * d.np, as = static_cast<int64_t>(d.mp) * d.mp;
+    d.x[0] = off;
+    d.x[1] = off + xs;
+    d.a = off + 2 * xs;
+    d.b = d.a + as;
+    off = d.b + as;
+    // T:optim/_muon.py _adjust_lr, in double as Python forms it
+    d.ratio[0] = std::sqrt(std::max(1.0, static_cast<double>(A) / static_cast<double>(B)));
+    d.ratio[1] = 0.2 * std::sqrt(static_cast<double>(std::max(A, B)));
+    desc[t] = d;
+    if (layout_out) {
+      const int64_t row[8] = {d.m, d.n, d.np, d.mp, d.x[0], d.x[1], d.a, d.b};
+      std::copy(row, row + 8, layout_out + 8 * t);
+    }
+  }
+  p->muon = desc;
+  p->muon_total = off;
+  if (total_out) *total_out = off;
+  if (p->kind != GS_DEV_HIP) return GS_OK;
+  // (tensor, tile) pairs, heaviest K first (stable: equal K keeps the list's order)
+  MuonTaskLists l;
+  for (int t = 0; t < p->n; ++t) {
+    const MuonDesc& d = desc[t];
+    const int tm = d.mp / kMuonTile, tn = d.np / kMuonTile;
+    for (int i = 0; i < tm; ++i)
+      for (int j = i; j < tm; ++j) l.gram.push_back(MuonTask{t, i, j, 0});
+    for (int i = 0; i < tm; ++i)
+      for (int j = 0; j < tn; ++j) l.apply.push_back(MuonTask{t, i, j, 0});
+    for (int i = 0; i < (d.A + kMuonEw - 1) / kMuonEw; ++i)
+      for (int j = 0; j < (d.B + kMuonEw - 1) / kMuonEw; ++j) l.ew.push_back(MuonTask{t, i, j, 0});
+  }
+  l.poly = l.gram;
+  auto by = [&](bool use_np) {
+    return [&desc, use_np](const MuonTask& a, const MuonTask& b) {
+      return (use_np ? desc[a.t].np : desc[a.t].mp) > (use_np ? desc[b.t].np : desc[b.t].mp);
+    };
+  };
+  std::stable_sort(l.gram.begin(), l.gram.end(), by(true));
+  std::stable_sort(l.poly.begin(), l.poly.end(), by(false));
+  std::stable_sort(l.apply.begin(), l.apply.end(), by(false));
+  return hip_muon_upload(p, l);
+}
+
+static int muon_ready(const gs_plan* p, const void* ws, int64_t ws_elems, int xsel, const char* who) {
+  const std::string w(who);
+  if (static_cast<int>(p->muon.size()) != p->n) return fail(GS_ESTATE, w + ": call gs_muon_layout first");
+  if (p->n != 0 && ws == nullptr) return fail(GS_EINVAL, w + ": NULL workspace");
+  if (ws_elems < p->muon_total)
+    return fail(GS_EINVAL, w + ": workspace of " + std::to_string(ws_elems) + " elements, the layout needs " +
+                               std::to_string(p->muon_total));
+  if ((reinterpret_cast<uintptr_t>(ws) & 15u) != 0) return fail(GS_EINVAL, w + ": workspace must be 16-B aligned");
+  if (xsel != 0 && xsel != 1) return fail(GS_EINVAL, w + ": xsel must be 0 or 1");
+  if (p->clip_on) return fail(GS_ESTATE, w + ": a gradient-norm clip is set on the plan; clipping is not part of Muon");
+  return GS_OK;
+}
+
+int gs_muon_prep(gs_plan* p, int grad_dtype, double momentum, int nesterov, double eps, float* norms_out, void* ws,
+                 int64_t ws_elems, void* stream) {
+  GsRange range("gs_muon_prep");
+  PLAN_OK(p);
+  GS_CHECK_ARG(is_float_dtype(grad_dtype), "gs_muon_prep: grad dtype must be f32, bf16 or f16");
+  GS_CHECK_ARG(p->n == 0 || norms_out != nullptr, "gs_muon_prep: NULL norms");
+  GS_CHECK_ARG(momentum >= 0 && eps >= 0, "gs_muon_prep: momentum and eps must be >= 0");
+  GS_TRY_RET(muon_ready(p, ws, ws_elems, 0, "gs_muon_prep"));
+  GS_TRY_RET(lars_slots_bound(p, 3, "gs_muon_prep"));
+  const MuonHyper h{static_cast<float>(1.0 - momentum), static_cast<float>(momentum), static_cast<float>(eps),
+                    nesterov != 0};
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_muon_prep(p, grad_dtype, h, norms_out, ws);
+  GS_TRY_RET(hip_muon_moments(p, grad_dtype, h, norms_out, stream));
+  return hip_muon_xwrite(p, grad_dtype, h, norms_out, ws, stream);
+}
+
+int gs_muon_gram(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double alpha, void* stream) {
+  GsRange range("gs_muon_gram");
+  PLAN_OK(p);
+  GS_TRY_RET(muon_ready(p, ws, ws_elems, xsel, "gs_muon_gram"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_muon_syrk(p, ws, 0, xsel, static_cast<float>(alpha), 0.f);
+  return hip_muon_syrk(p, ws, 0, xsel, static_cast<float>(alpha), 0.f, stream);
+}
+
+int gs_muon_poly(gs_plan* p, void* ws, int64_t ws_elems, double b, double c, void* stream) {
+  GsRange range("gs_muon_poly");
+  PLAN_OK(p);
+  GS_TRY_RET(muon_ready(p, ws, ws_elems, 0, "gs_muon_poly"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_muon_syrk(p, ws, 1, 0, static_cast<float>(c), static_cast<float>(b));
+  return hip_muon_syrk(p, ws, 1, 0, static_cast<float>(c), static_cast<float>(b), stream);
+}
+
+int gs_muon_apply(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double a, void* stream) {
+  GsRange range("gs_muon_apply");
+  PLAN_OK(p);
+  GS_TRY_RET(muon_ready(p, ws, ws_elems, xsel, "gs_muon_apply"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_muon_apply(p, ws, xsel, static_cast<float>(a));
+  return hip_muon_apply(p, ws, xsel, static_cast<float>(a), stream);
+}
+
+int gs_muon_update(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double lr, double weight_decay, int adjust,
+                   void* stream) {
+  GsRange range("gs_muon_update");
+  PLAN_OK(p);
+  GS_CHECK_ARG(adjust == 0 || adjust == 1, "gs_muon_update: adjust must be 0 (original) or 1 (match_rms_adamw)");
+  GS_TRY_RET(muon_ready(p, ws, ws_elems, xsel, "gs_muon_update"));
+  GS_TRY_RET(lars_slots_bound(p, 1, "gs_muon_update"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_muon_update(p, ws, xsel, lr, weight_decay, adjust);
+  return hip_muon_update(p, ws, xsel, lr, weight_decay, adjust, stream);
+}
+
 int gs_ema_step(gs_plan* p, int src_dtype, int lowp_dtype, double weight, int copy, void* stream) {
   GsRange range("gs_ema_step");
   PLAN_OK(p);

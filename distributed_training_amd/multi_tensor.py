@@ -360,6 +360,67 @@ class TensorListPlan:
             "gs_lamb_step",
         )
 
+    # ------------------------------------------------------------------ Muon
+    def muon_layout(self, rows: Sequence[int]) -> dict:
+        """Fix the plan's Muon workspace (gs_muon_layout): tensor t is the row-major
+        ``[rows[t], numel/rows[t]]`` matrix.  Returns ``{"total": bf16 elements of the
+        workspace, "tensors": [{"m", "n", "ldx", "lda", "x0", "x1", "agram", "bpoly"}]}``
+        (m <= n the X matrix's shape, ldx / lda the padded leading dimensions of X and of
+        Agram / Bpoly, the rest element offsets).  Allocate the workspace with
+        :meth:`muon_workspace`; not capturable (it uploads the task tables)."""
+        if len(rows) != self.n:
+            raise ValueError(f"plan has {self.n} tensors, got {len(rows)} row counts")
+        out = (ctypes.c_int64 * max(1, 8 * self.n))()
+        total = ctypes.c_int64()
+        L.check(L.lib().gs_muon_layout(self.handle, L.i64_array([int(r) for r in rows]), out, ctypes.byref(total)),
+                "gs_muon_layout")
+        keys = ("m", "n", "ldx", "lda", "x0", "x1", "agram", "bpoly")
+        self._muon = {"total": int(total.value),
+                      "tensors": [dict(zip(keys, (int(out[8 * t + k]) for k in range(8)))) for t in range(self.n)]}
+        return self._muon
+
+    def muon_workspace(self) -> torch.Tensor:
+        """A zero-filled bf16 workspace of the layout's size where the plan runs (the
+        kernels rely on the padding being zero and keep it so)."""
+        return torch.zeros(max(1, self._muon["total"]), dtype=torch.bfloat16, device=self.device)
+
+    def _muon_ws(self, ws: torch.Tensor):
+        if ws.dtype != torch.bfloat16 or not ws.is_contiguous() or not self._where_plan(ws):
+            raise ValueError("Muon workspace: contiguous bf16 where the plan runs")
+        return ws.data_ptr(), ws.numel()
+
+    def muon_prep(self, grad_dtype, momentum, nesterov, eps, norms: torch.Tensor, ws: torch.Tensor, stream=None):
+        """Slots 0 = p, 1 = g, 2 = momentum buffer: the buffer advances in place,
+        norms[2t + 1] = Σu² of tensor t's update direction, and X0 = bf16(u / max(‖u‖, eps))
+        lands in the workspace (gs_muon_prep)."""
+        self._norms_ok(norms)
+        ptr, n = self._muon_ws(ws)
+        L.check(L.lib().gs_muon_prep(self.handle, L.gs_dtype(grad_dtype), float(momentum), int(bool(nesterov)),
+                                     float(eps), norms.data_ptr(), ptr, n, self._stream(stream)), "gs_muon_prep")
+
+    def muon_gram(self, ws: torch.Tensor, xsel: int = 0, alpha: float = 1.0, stream=None):
+        """Agram = bf16(alpha * X·Xᵀ) of X buffer ``xsel``, every tensor in one launch (gs_muon_gram)."""
+        ptr, n = self._muon_ws(ws)
+        L.check(L.lib().gs_muon_gram(self.handle, ptr, n, int(xsel), float(alpha), self._stream(stream)), "gs_muon_gram")
+
+    def muon_poly(self, ws: torch.Tensor, b: float, c: float, stream=None):
+        """Bpoly = bf16(b * Agram + c * Agram·Agramᵀ) (gs_muon_poly)."""
+        ptr, n = self._muon_ws(ws)
+        L.check(L.lib().gs_muon_poly(self.handle, ptr, n, float(b), float(c), self._stream(stream)), "gs_muon_poly")
+
+    def muon_apply(self, ws: torch.Tensor, xsel: int, a: float, stream=None):
+        """X buffer ``1 - xsel`` = bf16(a * X + Bpoly·X) of X buffer ``xsel`` (gs_muon_apply)."""
+        ptr, n = self._muon_ws(ws)
+        L.check(L.lib().gs_muon_apply(self.handle, ptr, n, int(xsel), float(a), self._stream(stream)), "gs_muon_apply")
+
+    def muon_update(self, ws: torch.Tensor, xsel: int, lr, weight_decay, adjust_lr_fn=None, stream=None):
+        """p = p * (1 - lr*wd) - adjusted_lr * O, O = X buffer ``xsel`` in the parameter's
+        orientation; ``adjust_lr_fn`` as torch.optim.Muon's (gs_muon_update)."""
+        ptr, n = self._muon_ws(ws)
+        adjust = {None: 0, "original": 0, "match_rms_adamw": 1}[adjust_lr_fn]
+        L.check(L.lib().gs_muon_update(self.handle, ptr, n, int(xsel), float(lr), float(weight_decay), adjust,
+                                       self._stream(stream)), "gs_muon_update")
+
     # ------------------------------------------------------------------- EMA
     def ema(self, src_dtype, weight=0.0, copy=False, lowp_dtype=None, stream=None):
         """The weight average on slots 0 = average (fp32), 1 = source (``src_dtype``):

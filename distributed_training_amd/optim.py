@@ -17,6 +17,10 @@
   the moments and publishes the per-tensor ‖w‖², ‖update‖² (24 B/param), then
   one update pass (16 B/param) that recomputes the update and applies each
   tensor's trust ratio.
+* :class:`FusedMuon` — ``torch.optim.Muon`` semantics (T:optim/_muon.py): momentum,
+  then ``ns_steps`` Newton-Schulz iterations on bf16 MFMA, every stage one grouped
+  launch over the whole list of matrices (``3 * ns_steps + 3`` operations per step
+  instead of ~20 launches per parameter).
 * :func:`clip_grad_norm_` — ``torch.nn.utils.clip_grad_norm_``
   (T:nn/utils/clip_grad.py:50-186) with a wave-level Σg² reduction and the
   clip coefficient kept on the device (no host sync).
@@ -800,6 +804,115 @@ class FusedLAMB(_DeviceSteps, _FusedBase):
                               grad_scale=scale, found_inf=self.found_inf)
             plan.lamb(group["lr"], group["eps"], group["weight_decay"], bc1, bc2s, norms, lo, hi,
                       found_inf=self.found_inf)
+        return loss
+
+
+class FusedMuon(_FusedBase):
+    """Muon (``torch.optim.Muon``: signature, defaults, validation and the
+    ``momentum_buffer`` state key, so ``state_dict()`` moves between the two): SGD
+    momentum whose update matrix is orthogonalised by ``ns_steps`` quintic
+    Newton-Schulz iterations on bf16 operands.
+
+    torch runs about 20 launches per parameter and step (two lerps, cast, norm, div,
+    three GEMMs per iteration, two updates) and refuses ``foreach``.  Here every stage is
+    one grouped launch over the whole (param group, grad dtype) list, so a step is
+    ``3 * ns_steps + 3`` timed operations whatever the number of tensors:
+    ``gs_muon_prep`` (the segmented per-tensor Σu² pass LARS and LAMB share, which also
+    advances the momentum, then the pass that writes ``X = bf16(u / max(‖u‖, eps))``),
+    per iteration ``gs_muon_gram`` / ``gs_muon_poly`` / ``gs_muon_apply`` (bf16 MFMA,
+    fp32 accumulation, symmetric stages computed on the upper triangle only), and
+    ``gs_muon_update``.  The arithmetic is the contract in ``include/gsync.h``: torch's
+    rounding points, except that the norm is taken in fp32; the accumulation order
+    inside a product is the kernel's own, so results agree with torch to bf16 rounding,
+    not bit for bit, and are bit-reproducible run to run.
+
+    Parameters are fp32 and dense: 2-D, or — an extension over torch — 4-D conv filters
+    whose dim 0 has the largest stride.  Such a weight is the row-major matrix
+    ``[shape[0], numel / shape[0]]`` in memory order; for a ``channels_last`` filter
+    that is a column permutation of the logical flattening, which Newton-Schulz
+    commutes with.  Anything else raises ``ValueError``.  Grads are fp32, bf16 or fp16
+    in the parameter's layout; a parameter whose grad is None is skipped.
+    ``adjust_lr_fn`` is torch's (``None`` / ``"original"``, ``"match_rms_adamw"``) with
+    ``A = shape[0]``, ``B = numel / shape[0]``.
+
+    The usual composition keeps everything that is not a filter off Muon::
+
+        filters = [p for p in model.parameters() if p.ndim == 4]
+        rest = [p for p in model.parameters() if p.ndim != 4]   # BatchNorm, biases, fc
+        opts = [FusedMuon(filters, lr=0.02), FusedAdamW(rest, lr=1e-3)]   # or FusedSGD
+
+    Out of scope, each an error: ``grad_scale`` / ``found_inf`` (AMP), ``capturable=True``,
+    ``max_grad_norm``, ZeRO sharding of Muon (a matrix split across ranks), the DeepSpeed /
+    ColossalAI shims, ``DDP._register_fused_optim``.
+    """
+
+    _name = "FusedMuon"
+    _timer_kinds = (L.GS_OP_MUON_PREP, L.GS_OP_MUON_GRAM, L.GS_OP_MUON_POLY, L.GS_OP_MUON_APPLY,
+                    L.GS_OP_MUON_UPDATE)
+
+    def __init__(self, params, lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True,
+                 ns_coefficients=(3.4445, -4.7750, 2.0315), eps=1e-7, ns_steps=5, adjust_lr_fn=None,
+                 *, capturable=False, max_grad_norm=None):
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 <= lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 <= momentum:
+            raise ValueError(f"momentum should be >= 0 but is: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight decay should be >= 0 but is: {weight_decay}")
+        if adjust_lr_fn is not None and adjust_lr_fn not in ["original", "match_rms_adamw"]:
+            raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+        if capturable:
+            raise ValueError("FusedMuon does not support capturable=True")
+        if max_grad_norm:
+            raise ValueError("FusedMuon does not support max_grad_norm (clip the grads before the step)")
+        defaults = dict(lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
+                        ns_coefficients=ns_coefficients, eps=eps, ns_steps=ns_steps, adjust_lr_fn=adjust_lr_fn)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.ndim not in (2, 4):
+                    raise ValueError("FusedMuon only supports 2D parameters and 4D conv filters whereas we found "
+                                     f"a parameter with size: {p.size()}")
+                if p.numel() == 0 or not is_dense(p) or p.stride(0) * p.shape[0] != p.numel():
+                    raise ValueError("FusedMuon: dim 0 of a parameter must be its outermost dimension in memory "
+                                     f"(size {tuple(p.size())}, strides {p.stride()})")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self.grad_scale is not None or self.found_inf is not None:
+            raise RuntimeError("FusedMuon does not support grad_scale / found_inf (unscale the grads and skip "
+                               "the step on the host)")
+        for group in self.param_groups:
+            coef = tuple(group["ns_coefficients"])
+            if group["ns_steps"] >= 100:
+                raise ValueError("Number of steps must be less than 100 for computational efficiency")
+            if len(coef) != 3:
+                raise ValueError("Coefficients must be a tuple of exactly 3 values")
+            a, b, c = coef
+            # torch's Muon keeps the buffer whatever the momentum (lerp with weight 1 at 0)
+            for gdt, (ps, gs, bs) in self._collect(dict(group, momentum=1.0)).items():
+                plan = self._plans.get(ps)
+                for slot, lst in enumerate((ps, gs, bs)):
+                    plan.set_ptrs(slot, lst)
+                ws = getattr(plan, "_muon_space", None)
+                if ws is None:
+                    plan.muon_layout([p.shape[0] for p in ps])
+                    ws = plan._muon_space = plan.muon_workspace()
+                    plan._norms = torch.zeros(2 * len(ps), dtype=torch.float32, device=ps[0].device)
+                plan.muon_prep(gdt, group["momentum"], group["nesterov"], group["eps"], plan._norms, ws)
+                x = 0
+                for _ in range(int(group["ns_steps"])):
+                    plan.muon_gram(ws, x)
+                    plan.muon_poly(ws, b, c)
+                    plan.muon_apply(ws, x, a)
+                    x ^= 1
+                plan.muon_update(ws, x, group["lr"], group["weight_decay"], group["adjust_lr_fn"])
         return loss
 
 

@@ -210,6 +210,11 @@ int64_t gs_plan_task_units(gs_plan* p);
 #define GS_OP_LAMB_MOMENTS 11 /* gs_lamb_moments: the chunk pass and its fold, one record */
 #define GS_OP_LAMB 12
 #define GS_OP_EMA 13
+#define GS_OP_MUON_PREP 14 /* gs_muon_prep: the segmented pass (one record), then the X pass (one record) */
+#define GS_OP_MUON_GRAM 15
+#define GS_OP_MUON_POLY 16
+#define GS_OP_MUON_APPLY 17
+#define GS_OP_MUON_UPDATE 18
 int gs_plan_timer_enable(gs_plan* p, int n_slots);
 int gs_plan_timer_read(gs_plan* p, float* ms_out, int32_t* kind_out, int cap);
 /* register the per-tensor pointers of one slot (uploads on change, ordered on `stream`) */
@@ -511,6 +516,65 @@ int gs_lamb_step_lowp(gs_plan* p, int lowp_dtype, double lr, double eps, double 
  * replaces: the host-side `state["step"] += 1` and bias corrections of a Python LAMB */
 int gs_lamb_hyper(int device_kind, double* step, const double* lr, double beta1, double beta2, int bias_correction,
                   const float* found_inf, float* hyper, void* stream);
+
+/* Muon (Jordan et al. 2024; torch.optim.Muon): SGD momentum whose update matrix is
+ * orthogonalised by a quintic Newton-Schulz iteration on bf16 operands.  One plan holds a
+ * ragged list of matrices; every stage is ONE grouped launch over the whole list, so a
+ * step is 3*ns_steps + 3 timed operations whatever the number of tensors (gs_muon_prep is
+ * two of them, and its first, the segmented pass, is the chunk kernel and its fold):
+ *   gs_muon_prep, ns_steps x (gs_muon_gram, gs_muon_poly, gs_muon_apply), gs_muon_update.
+ *
+ * Tensor t is the row-major [A, B] matrix in memory (A = rows[t] of gs_muon_layout,
+ * B = numel/A).  Slots: 0 = p (f32), 1 = g (grad_dtype: f32, bf16 or f16), 2 = the momentum
+ * buffer (f32).  Arithmetic, per tensor (w1 = float(1-momentum) formed in double):
+ *   buf = lerp(buf, g, w1)                       torch.lerp's form (gs_ema_step's), fp32
+ *   u   = nesterov ? lerp(g, buf, momentum) : buf
+ *   s   = 1 / max(sqrt(Σu²), eps)                fp32; Σu² by the segmented pass of
+ *                                                gs_lars_norms (same slot map and order)
+ *   X   = bf16(u*s), stored [m, n], m = min(A,B), n = max(A,B) (transposed when A > B).
+ *         The scale is applied HERE, in the pass that writes X (not folded into the
+ *         first Gram): one fp32 multiply, one rounding to bf16.
+ *   repeat ns_steps times:
+ *     Agram = bf16(alpha * (X·Xᵀ))               gs_muon_gram (alpha = 1 in a step)
+ *     Bpoly = bf16(fma(c, Agram·Agramᵀ, b*Agram)) gs_muon_poly
+ *     X'    = bf16(fma(a, X, Bpoly·X))           gs_muon_apply (the other X buffer)
+ *   O   = X, read back through the transpose when A > B
+ *   p   = p*float(1 - lr*wd) - float(lr*ratio)*O  gs_muon_update; both factors formed in
+ *         double; ratio = sqrt(max(1, A/B)) ("original") or 0.2*sqrt(max(A, B)) ("match_rms_adamw")
+ * Every product is a sum of bf16 x bf16 products accumulated in fp32 (bf16 MFMA on the
+ * device); each stored value is rounded once, to nearest even.  These are torch's rounding
+ * points, except that torch takes the norm and the division in bf16.  The order of
+ * accumulation inside a product is the kernel's own (K in ascending 32-slabs, the MFMA's
+ * order inside a slab), so the device is not bit-comparable to torch nor to the host
+ * backend (ascending k, one fp32 add per product) — unlike the other ops of this library,
+ * host and device agree here only to the accumulation order.  The device result is
+ * bit-reproducible run to run: K is never split across workgroups, no atomics.
+ * Agram and Bpoly are exactly symmetric: only tiles on or above the diagonal are
+ * computed and the mirror tile is written from the same accumulators.
+ *
+ * Workspace (bf16, caller-owned, zero-filled once by the caller): per tensor X0, X1
+ * [mp, np], Agram, Bpoly [mp, mp], mp / np = m / n rounded up to 128.  The kernels never
+ * write a non-zero value into the padding and zero rows / columns stay zero through every
+ * stage, so padding is exact and the GEMM kernels have no edge predicate.
+ * gs_muon_layout fixes it: layout_out[8t..8t+7] = m, n, ldx (= np), lda (= mp), and the
+ * element offsets of X0, X1, Agram, Bpoly; *total_out = the workspace's elements.  On a HIP
+ * plan it uploads the task tables (synchronous: not capturable).
+ * xsel (0 / 1) names the X buffer a stage reads; gs_muon_prep writes X0, gs_muon_apply
+ * writes the other one.  ws_elems is checked against the layout's total.
+ *
+ * Not part of Muon here: grad_scale / found_inf, a plan clip (GS_ESTATE), a hyper source.
+ * replaces: T:optim/_muon.py _single_tensor_muon / _zeropower_via_newtonschulz (per
+ *           parameter: 2 lerps, cast, norm, div, 3 GEMMs x ns_steps, mul_, add_) */
+int gs_muon_layout(gs_plan* p, const int64_t* rows, int64_t* layout_out, int64_t* total_out);
+/* norms_out: fp32[2n] in the plan's memory kind: [2t] = Σbuf², [2t+1] = Σu² */
+int gs_muon_prep(gs_plan* p, int grad_dtype, double momentum, int nesterov, double eps, float* norms_out,
+                 void* ws, int64_t ws_elems, void* stream);
+int gs_muon_gram(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double alpha, void* stream);
+int gs_muon_poly(gs_plan* p, void* ws, int64_t ws_elems, double b, double c, void* stream);
+int gs_muon_apply(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double a, void* stream);
+/* adjust: 0 = "original", 1 = "match_rms_adamw" */
+int gs_muon_update(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double lr, double weight_decay, int adjust,
+                   void* stream);
 
 /* EMA / SWA weight averaging: one pass a' = lerp(a, s, w) over a whole model.
  * Slots: 0 = the average a (f32), 1 = the source s (src_dtype: f32, bf16 or f16, converted
