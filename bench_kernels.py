@@ -507,6 +507,9 @@ def main():
         rec("adam", 28 * n, *timeit(fadam.step, args.iters), "torch.optim.Adam fused")
     if want("muon"):
         muon_row(args, dev, shapes)
+    if want("psgd"):
+        for rank in (1, 4):
+            psgd_row(args, dev, rank)
 
 
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X dense bf16 matrix peak (AMD's data sheet: 2.5 PFLOP/s)
@@ -552,6 +555,74 @@ def muon_row(args, dev, shapes, ns_steps=5, repeats=5):
            "ns_gflop": flop / 1e9, "fused_ns_tflops": flop / (med(t_f) * 1e-3) / 1e12,
            "fused_frac_of_bf16_peak": flop / (med(t_f) * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS,
            "speedup": med(t_t) / med(t_f)}
+    print(json.dumps(row), flush=True)
+
+
+def psgd_row(args, dev, rank, repeats=5):
+    """The fused powerSGD_hook against torch's on the model's DDP bucket layout (1 MiB first
+    bucket, 25 MiB after, reverse parameter order) at world size 1: both in this process,
+    alternating, each repeat `iters` steps' worth of buckets between one pair of device
+    events after a warm-up and a synchronise.  One JSON line: ms per step of both (median
+    over the repeats, and every repeat), the launch count of the fused path and its achieved
+    HBM rate over the 7 words per compressed gradient element the stages move."""
+    import torch.distributed as dist
+    from torch.distributed.algorithms.ddp_comm_hooks import powerSGD_hook as T
+
+    import distributed_training_amd as D
+    from distributed_training_amd.resnet import MODELS
+
+    if not dist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29531")
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    params = list(MODELS[args.model]().to(dev).parameters())
+    order = list(reversed(range(len(params))))
+    layout = D.compute_bucket_assignment_by_size(params, [1 << 20, 25 << 20], order)
+    g = torch.Generator(device=dev).manual_seed(2)
+
+    def buckets():
+        out = []
+        for bi, idx in enumerate(layout):
+            offs, total = [], 0
+            for i in idx:
+                offs.append(total)
+                total += params[i].numel()
+            out.append(D.GradBucket(bi, torch.empty(total, device=dev), [params[i] for i in idx], offs,
+                                    bi == len(layout) - 1))
+        return out
+
+    sides = {"fused": (D.PowerSGDState(None, matrix_approximation_rank=rank, start_powerSGD_iter=2), D.powerSGD_hook,
+                       buckets()),
+             "torch": (T.PowerSGDState(None, matrix_approximation_rank=rank, start_powerSGD_iter=2), T.powerSGD_hook,
+                       buckets())}
+    fresh = [torch.randn(b.buffer().numel(), device=dev, generator=g) * 0.01 for b in sides["fused"][2]]
+    for state, _, _ in sides.values():
+        state.iter = state.start_powerSGD_iter
+
+    def step(side):
+        state, hook, bs = sides[side]
+        for b, src in zip(bs, fresh):  # a new gradient in the bucket (part of both sides' time)
+            b.buffer().copy_(src)
+            hook(state, b).wait()
+
+    times = {k: [] for k in sides}
+    for _ in range(repeats):
+        for side in sides:
+            for _ in range(3):
+                step(side)
+            torch.cuda.synchronize()
+            times[side].append(timeit_batched(lambda: step(side), args.iters))
+    med = lambda ts: sorted(ts)[len(ts) // 2]  # noqa: E731
+    ctxs = sides["fused"][0]._ctx.values()
+    comp = sum(int(c.error.numel()) for c in ctxs)
+    row = {"kernel": "psgd_hook", "model": args.model, "rank": rank, "buckets": len(layout), "tag": args.tag,
+           "compressed_elems": comp, "total_elems": sum(p.numel() for p in params),
+           "fused_ms": med(times["fused"]), "torch_ms": med(times["torch"]),
+           "fused_ms_repeats": times["fused"], "torch_ms_repeats": times["torch"],
+           "fused_launches": sum(6 * (c.n_comp > 0) + 2 * (c.rest_plan.n > 0) for c in ctxs),
+           "fused_GBps": 7 * 4 * comp / (med(times["fused"]) * 1e-3) / 1e9,
+           "fused_frac_of_8TBps": 7 * 4 * comp / (med(times["fused"]) * 1e-3) / 1e9 / HBM_PEAK,
+           "speedup": med(times["torch"]) / med(times["fused"])}
     print(json.dumps(row), flush=True)
 
 

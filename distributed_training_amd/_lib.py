@@ -44,6 +44,7 @@ GS_OP_LARS_NORM, GS_OP_LARS = 9, 10
 GS_OP_LAMB_MOMENTS, GS_OP_LAMB = 11, 12
 GS_OP_EMA = 13
 GS_OP_MUON_PREP, GS_OP_MUON_GRAM, GS_OP_MUON_POLY, GS_OP_MUON_APPLY, GS_OP_MUON_UPDATE = 14, 15, 16, 17, 18
+GS_OP_PSGD_ORTH, GS_OP_PSGD_PROJECT, GS_OP_PSGD_BACKPROJECT, GS_OP_PSGD_RECONSTRUCT = 19, 20, 21, 22
 GS_EMA_EMA, GS_EMA_SWA, GS_EMA_WARMUP = 0, 1, 2
 
 _TORCH_TO_GS = {
@@ -168,6 +169,11 @@ SIGNATURES = {
     "gs_muon_poly": (_c_int, [_vp, _vp, _c_i64, _c_d, _c_d, _vp]),
     "gs_muon_apply": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_d, _vp]),
     "gs_muon_update": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_d, _c_d, _c_int, _vp]),
+    "gs_psgd_layout": (_c_int, [_vp, _vp, _c_int, _vp, _vp]),
+    "gs_psgd_orthogonalize": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_d, _vp]),
+    "gs_psgd_project": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "gs_psgd_backproject": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "gs_psgd_reconstruct": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_d, _vp]),
     "gs_lars_step": (_c_int, [_vp, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp, _vp]),
     "gs_lars_step_lowp": (_c_int, [_vp, _c_int, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp, _vp]),
     "gs_lamb_step_lowp": (_c_int, [_vp, _c_int, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _vp]),

@@ -155,6 +155,37 @@ struct MuonTables {  // device (HIP plans) or host pointers
   int32_t n_sym, n_apply, n_ew;
 };
 
+// ---- PowerSGD (gs_psgd_*: gs_psgd_kernels.hip / gs_host.cpp) ----
+// Tensor t of the plan is the row-major [n, m] matrix in memory; its factors are P [n, r]
+// and Q [m, r], r = min(n, m, rank), row-major at p_off / q_off of the caller's P and Q
+// memory (tensors in plan order, no padding: torch's p_memory / q_memory layout).
+constexpr int kPsgdMaxRank = 8;
+constexpr int kPsgdRows = 128;        // row block: P rows in LDS (project's is prb <= this, per tensor)
+constexpr int kPsgdCols = 1024;       // project: columns of Q staged in LDS at a time (4 float4 sweeps of a wave)
+constexpr int kPsgdStrip = 64;        // backproject / reconstruct: a wave's 256-byte row segment
+constexpr int kPsgdOrthLds = 36864;   // orthogonalize: floats of a factor kept in LDS (4608 x 8: 144 KiB)
+struct PsgdDesc {
+  int64_t p_off, q_off, part_off;  // part_off: the row blocks' partial Q sums (backproject's scratch)
+  int32_t n, m, r;
+  int32_t sub;   // project: lanes that share a row (64, or the power of two covering m / 4)
+  int32_t prb;   // project: rows per workgroup (a multiple of 4 * 64 / sub)
+  int32_t nrb;   // row blocks of kPsgdRows
+};
+struct PsgdTask {
+  int32_t t, i, j, pad_;  // tensor, row block, column strip
+};
+struct PsgdTables {  // device pointers (HIP plans)
+  const PsgdDesc* desc;
+  const PsgdTask* proj;   // (tensor, block of prb rows), most columns first
+  const PsgdTask* back;   // (tensor, row block, strip), in plan order: equal tasks
+  const PsgdTask* fold;   // (tensor, 256 elements of Q)
+  const PsgdTask* recon;  // (tensor, strip), most rows first
+  const PsgdTask* orth[2];  // (tensor): P by n * r, Q by m * r, largest first
+  double* part;           // backproject's partial sums
+  int32_t n_proj, n_back, n_fold, n_recon, n_orth;
+  int32_t orth_lds[2];    // dynamic LDS bytes of the two orthogonalize launches
+};
+
 }  // namespace gs
 
 // The opaque plan (visible to every TU of the library).
@@ -217,6 +248,13 @@ struct gs_plan {
   int64_t muon_total = 0;   // workspace elements (bf16)
   void* d_muon = nullptr;
   gs::MuonTables muon_tab{};
+  // PowerSGD (gs_psgd_layout): the factor layout and, on HIP plans, its device copy with
+  // the task tables and the backproject scratch
+  std::vector<gs::PsgdDesc> psgd;
+  int psgd_rp = 0;                   // the rank rounded up to 1, 2, 4 or 8 (the kernels' template)
+  int64_t psgd_p = 0, psgd_q = 0;    // elements of the P and Q memory
+  void* d_psgd = nullptr;
+  gs::PsgdTables psgd_tab{};
   // launch timer ring (gs_plan_timer_enable)
   std::vector<void*> timer_ev;  // [2 * slots]: start, stop
   std::vector<int32_t> timer_kind;  // [slots]: GS_OP_* of the timed launch
@@ -614,6 +652,20 @@ int host_muon_prep(gs_plan* p, int gdt, const MuonHyper& h, float* norms, void* 
 int host_muon_syrk(gs_plan* p, void* ws, int poly, int xsel, float alpha, float beta);
 int host_muon_apply(gs_plan* p, void* ws, int xsel, float a);
 int host_muon_update(gs_plan* p, void* ws, int xsel, double lr, double wd, int adjust);
+// gs_psgd_kernels.hip; task tables built by gs_psgd_layout (gs_plan.cpp)
+struct PsgdTaskLists {
+  std::vector<PsgdTask> proj, back, fold, recon, orth[2];
+  int64_t part_elems = 0;
+};
+int hip_psgd_upload(gs_plan* p, const PsgdTaskLists& l);
+int hip_psgd_orthogonalize(gs_plan* p, int which, float* mem, float eps, void* stream);
+int hip_psgd_project(gs_plan* p, int use_error, float* pmem, const float* qmem, void* stream);
+int hip_psgd_backproject(gs_plan* p, const float* pmem, float* qmem, void* stream);
+int hip_psgd_reconstruct(gs_plan* p, const float* pmem, float* qmem, float inv_ws, void* stream);
+int host_psgd_orthogonalize(gs_plan* p, int which, float* mem, float eps);
+int host_psgd_project(gs_plan* p, int use_error, float* pmem, const float* qmem);
+int host_psgd_backproject(gs_plan* p, const float* pmem, float* qmem);
+int host_psgd_reconstruct(gs_plan* p, const float* pmem, float* qmem, float inv_ws);
 int hip_device_count();
 int hip_memset_async(void* dst, int value, size_t bytes, void* stream);
 int hip_stream_wait(void* waiter, void* signaler);

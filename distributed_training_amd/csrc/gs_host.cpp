@@ -559,6 +559,87 @@ int host_muon_update(gs_plan* p, void* ws, int xsel, double lr, double wd, int a
   return GS_OK;
 }
 
+// PowerSGD on the host (include/gsync.h, gs_psgd_*): the device stages restated as plain loops
+// with the same rounding points (every sum of products in fp64, rounded to fp32 once where it
+// is stored; the division and the square root of the orthogonalisation), every sum in
+// ascending index order — a fixed order that is not the kernels', so host and device agree
+// to the accumulation order of the fp64 sums only.  Serial: the sizes
+// that reach the host backend are test sizes and gloo rehearsals.
+int host_psgd_orthogonalize(gs_plan* p, int which, float* mem, float eps) {
+  for (const PsgdDesc& d : p->psgd) {
+    const int64_t rows = which ? d.m : d.n, r = d.r;
+    float* X = mem + (which ? d.q_off : d.p_off);
+    for (int64_t i = 0; i < r; ++i) {
+      double nn = 0.0;  // the sums in fp64, rounded once, as on the device
+      for (int64_t k = 0; k < rows; ++k) nn = nn + static_cast<double>(X[k * r + i]) * static_cast<double>(X[k * r + i]);
+      const float nrm = static_cast<float>(std::sqrt(nn)) + eps;
+      for (int64_t k = 0; k < rows; ++k) X[k * r + i] = X[k * r + i] / nrm;
+      for (int64_t j = i + 1; j < r; ++j) {
+        double dd = 0.0;
+        for (int64_t k = 0; k < rows; ++k) dd = dd + static_cast<double>(X[k * r + i]) * static_cast<double>(X[k * r + j]);
+        const float dot = static_cast<float>(dd);
+        for (int64_t k = 0; k < rows; ++k) X[k * r + j] = X[k * r + j] - dot * X[k * r + i];
+      }
+    }
+  }
+  return GS_OK;
+}
+
+int host_psgd_project(gs_plan* p, int use_error, float* pmem, const float* qmem) {
+  for (int t = 0; t < p->n; ++t) {
+    const PsgdDesc& d = p->psgd[t];
+    const float* M = static_cast<const float*>(slot(p, 0, t));
+    float* E = static_cast<float*>(slot(p, 1, t));
+    const float* Q = qmem + d.q_off;
+    for (int64_t i = 0; i < d.n; ++i) {
+      double acc[kPsgdMaxRank] = {};
+      for (int64_t c = 0; c < d.m; ++c) {
+        const float e = use_error ? M[i * d.m + c] + E[i * d.m + c] : M[i * d.m + c];
+        E[i * d.m + c] = e;
+        for (int j = 0; j < d.r; ++j) acc[j] = acc[j] + static_cast<double>(e) * static_cast<double>(Q[c * d.r + j]);
+      }
+      for (int j = 0; j < d.r; ++j) pmem[d.p_off + i * d.r + j] = static_cast<float>(acc[j]);
+    }
+  }
+  return GS_OK;
+}
+
+int host_psgd_backproject(gs_plan* p, const float* pmem, float* qmem) {
+  for (int t = 0; t < p->n; ++t) {
+    const PsgdDesc& d = p->psgd[t];
+    const float* E = static_cast<const float*>(slot(p, 1, t));
+    const float* P = pmem + d.p_off;
+    float* Q = qmem + d.q_off;
+    std::vector<double> acc(static_cast<size_t>(d.m) * d.r, 0.0);
+    for (int64_t i = 0; i < d.n; ++i)
+      for (int64_t c = 0; c < d.m; ++c)
+        for (int j = 0; j < d.r; ++j)
+          acc[c * d.r + j] = acc[c * d.r + j] + static_cast<double>(E[i * d.m + c]) * static_cast<double>(P[i * d.r + j]);
+    for (size_t e = 0; e < acc.size(); ++e) Q[e] = static_cast<float>(acc[e]);
+  }
+  return GS_OK;
+}
+
+int host_psgd_reconstruct(gs_plan* p, const float* pmem, float* qmem, float inv_ws) {
+  for (int t = 0; t < p->n; ++t) {
+    const PsgdDesc& d = p->psgd[t];
+    float* G = static_cast<float*>(slot(p, 0, t));
+    float* E = static_cast<float*>(slot(p, 1, t));
+    const float* P = pmem + d.p_off;
+    float* Q = qmem + d.q_off;
+    for (int64_t e = 0; e < static_cast<int64_t>(d.m) * d.r; ++e) Q[e] = Q[e] * inv_ws;
+    for (int64_t i = 0; i < d.n; ++i)
+      for (int64_t c = 0; c < d.m; ++c) {
+        double s = 0.0;  // fp64 products are exact; one rounding to fp32, as on the device
+        for (int j = 0; j < d.r; ++j) s = s + static_cast<double>(P[i * d.r + j]) * static_cast<double>(Q[c * d.r + j]);
+        const float a = static_cast<float>(s);
+        G[i * d.m + c] = a;
+        E[i * d.m + c] = E[i * d.m + c] - a;
+      }
+  }
+  return GS_OK;
+}
+
 // A pairwise sum of terms pushed one by one: a binary counter of finished subtrees, small ones
 // folded first, so at most ceil(log2 n) roundings lie on any path, as in the device's tree
 // (gs_wave.h); its order differs from the device's.

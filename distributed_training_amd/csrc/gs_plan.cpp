@@ -803,6 +803,128 @@ int gs_muon_update(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double lr, 
   return hip_muon_update(p, ws, xsel, lr, weight_decay, adjust, stream);
 }
 
+// ---- PowerSGD: the factor layout and the task tables of the grouped launches ----
+int gs_psgd_layout(gs_plan* p, const int64_t* rows, int rank, int64_t* layout_out, int64_t* totals_out) {
+  PLAN_OK(p);
+  GS_CHECK_ARG(p->n == 0 || rows != nullptr, "gs_psgd_layout: NULL rows");
+  GS_CHECK_ARG(rank >= 1 && rank <= kPsgdMaxRank, "gs_psgd_layout: the rank must be 1.." + std::to_string(kPsgdMaxRank));
+  std::vector<PsgdDesc> desc(p->n);
+  int64_t po = 0, qo = 0;
+  PsgdTaskLists l;
+  for (int t = 0; t < p->n; ++t) {
+    const int64_t n = rows[t], numel = p->numel[t];
+    if (n <= 0 || numel <= 0 || numel % n != 0 || numel > (int64_t(1) << 30))
+      return fail(GS_EINVAL, "gs_psgd_layout: tensor " + std::to_string(t) + " is not an [n, m] matrix (rows " +
+                                 std::to_string(n) + ", numel " + std::to_string(numel) + ")");
+    PsgdDesc d{};
+    d.n = static_cast<int32_t>(n);
+    d.m = static_cast<int32_t>(numel / n);
+    d.r = std::min(std::min(d.n, d.m), static_cast<int32_t>(rank));
+    d.p_off = po;
+    d.q_off = qo;
+    d.part_off = l.part_elems;
+    po += static_cast<int64_t>(d.n) * d.r;
+    qo += static_cast<int64_t>(d.m) * d.r;
+    // project: the lanes of a row and, from them, rows per workgroup of about 32 Ki elements
+    d.sub = 64;
+    if (d.m <= 128)
+      for (d.sub = 2; d.sub * 4 < d.m; d.sub *= 2) {}
+    const int step = 4 * (64 / d.sub);
+    d.prb = std::min(kPsgdRows, std::max(step, (32768 / d.m + step - 1) / step * step));
+    d.nrb = (d.n + kPsgdRows - 1) / kPsgdRows;
+    l.part_elems += static_cast<int64_t>(d.nrb) * d.m * d.r;
+    desc[t] = d;
+    if (layout_out) {
+      const int64_t row[5] = {d.n, d.m, d.r, d.p_off, d.q_off};
+      std::copy(row, row + 5, layout_out + 5 * t);
+    }
+  }
+  p->psgd = desc;
+  p->psgd_rp = rank <= 2 ? rank : (rank <= 4 ? 4 : 8);
+  p->psgd_p = po;
+  p->psgd_q = qo;
+  if (totals_out) {
+    totals_out[0] = po;
+    totals_out[1] = qo;
+  }
+  if (p->kind != GS_DEV_HIP) return GS_OK;
+  for (int t = 0; t < p->n; ++t) {
+    const PsgdDesc& d = desc[t];
+    const int strips = (d.m + kPsgdStrip - 1) / kPsgdStrip;
+    for (int i = 0; i * d.prb < d.n; ++i) l.proj.push_back(PsgdTask{t, i, 0, 0});
+    for (int i = 0; i < d.nrb; ++i)
+      for (int j = 0; j < strips; ++j) l.back.push_back(PsgdTask{t, i, j, 0});
+    for (int64_t i = 0; i * kBlock < static_cast<int64_t>(d.m) * d.r; ++i)
+      l.fold.push_back(PsgdTask{t, static_cast<int32_t>(i), 0, 0});
+    for (int j = 0; j < strips; ++j) l.recon.push_back(PsgdTask{t, 0, j, 0});
+    l.orth[0].push_back(PsgdTask{t, 0, 0, 0});
+    l.orth[1].push_back(PsgdTask{t, 0, 0, 0});
+  }
+  // heaviest first (stable: equal weights keep the list's order)
+  auto by = [&desc](auto weight) {
+    return [&desc, weight](const PsgdTask& a, const PsgdTask& b) { return weight(desc[a.t]) > weight(desc[b.t]); };
+  };
+  std::stable_sort(l.proj.begin(), l.proj.end(), by([](const PsgdDesc& d) { return int64_t(d.prb) * d.m; }));
+  std::stable_sort(l.recon.begin(), l.recon.end(), by([](const PsgdDesc& d) { return int64_t(d.n); }));
+  std::stable_sort(l.orth[0].begin(), l.orth[0].end(), by([](const PsgdDesc& d) { return int64_t(d.n) * d.r; }));
+  std::stable_sort(l.orth[1].begin(), l.orth[1].end(), by([](const PsgdDesc& d) { return int64_t(d.m) * d.r; }));
+  return hip_psgd_upload(p, l);
+}
+
+static int psgd_ready(const gs_plan* p, const float* pmem, int64_t p_elems, const float* qmem, int64_t q_elems,
+                      int n_slots, const char* who) {
+  const std::string w(who);
+  if (static_cast<int>(p->psgd.size()) != p->n || p->psgd_rp == 0) return fail(GS_ESTATE, w + ": call gs_psgd_layout first");
+  if (p->n != 0 && ((pmem == nullptr && p_elems >= 0) || (qmem == nullptr && q_elems >= 0)))
+    return fail(GS_EINVAL, w + ": NULL factor memory");
+  if ((p_elems >= 0 && p_elems < p->psgd_p) || (q_elems >= 0 && q_elems < p->psgd_q))
+    return fail(GS_EINVAL, w + ": factor memory of " + std::to_string(p_elems) + " / " + std::to_string(q_elems) +
+                               " elements, the layout needs " + std::to_string(p->psgd_p) + " / " +
+                               std::to_string(p->psgd_q));
+  return lars_slots_bound(p, n_slots, who);
+}
+
+int gs_psgd_orthogonalize(gs_plan* p, int which, float* mem, int64_t mem_elems, double eps, void* stream) {
+  GsRange range("gs_psgd_orthogonalize");
+  PLAN_OK(p);
+  GS_CHECK_ARG(which == 0 || which == 1, "gs_psgd_orthogonalize: which must be 0 (P) or 1 (Q)");
+  GS_CHECK_ARG(eps >= 0, "gs_psgd_orthogonalize: eps must be >= 0");
+  GS_TRY_RET(which ? psgd_ready(p, nullptr, -1, mem, mem_elems, 0, "gs_psgd_orthogonalize")
+                   : psgd_ready(p, mem, mem_elems, nullptr, -1, 0, "gs_psgd_orthogonalize"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_psgd_orthogonalize(p, which, mem, static_cast<float>(eps));
+  return hip_psgd_orthogonalize(p, which, mem, static_cast<float>(eps), stream);
+}
+
+int gs_psgd_project(gs_plan* p, int use_error, float* pmem, int64_t p_elems, const float* qmem, int64_t q_elems,
+                    void* stream) {
+  GsRange range("gs_psgd_project");
+  PLAN_OK(p);
+  GS_TRY_RET(psgd_ready(p, pmem, p_elems, qmem, q_elems, 2, "gs_psgd_project"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_psgd_project(p, use_error != 0, pmem, qmem);
+  return hip_psgd_project(p, use_error != 0, pmem, qmem, stream);
+}
+
+int gs_psgd_backproject(gs_plan* p, const float* pmem, int64_t p_elems, float* qmem, int64_t q_elems, void* stream) {
+  GsRange range("gs_psgd_backproject");
+  PLAN_OK(p);
+  GS_TRY_RET(psgd_ready(p, pmem, p_elems, qmem, q_elems, 2, "gs_psgd_backproject"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_psgd_backproject(p, pmem, qmem);
+  return hip_psgd_backproject(p, pmem, qmem, stream);
+}
+
+int gs_psgd_reconstruct(gs_plan* p, const float* pmem, int64_t p_elems, float* qmem, int64_t q_elems, double inv_ws,
+                        void* stream) {
+  GsRange range("gs_psgd_reconstruct");
+  PLAN_OK(p);
+  GS_TRY_RET(psgd_ready(p, pmem, p_elems, qmem, q_elems, 2, "gs_psgd_reconstruct"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_psgd_reconstruct(p, pmem, qmem, static_cast<float>(inv_ws));
+  return hip_psgd_reconstruct(p, pmem, qmem, static_cast<float>(inv_ws), stream);
+}
+
 int gs_ema_step(gs_plan* p, int src_dtype, int lowp_dtype, double weight, int copy, void* stream) {
   GsRange range("gs_ema_step");
   PLAN_OK(p);

@@ -421,6 +421,57 @@ class TensorListPlan:
         L.check(L.lib().gs_muon_update(self.handle, ptr, n, int(xsel), float(lr), float(weight_decay), adjust,
                                        self._stream(stream)), "gs_muon_update")
 
+    # -------------------------------------------------------------- PowerSGD
+    def psgd_layout(self, rows: Sequence[int], rank: int) -> dict:
+        """Fix the plan's PowerSGD factors (gs_psgd_layout): tensor t is the row-major
+        ``[rows[t], numel/rows[t]]`` matrix, compressed to rank ``r = min(n, m, rank)``.
+        Returns ``{"p_total", "q_total", "tensors": [{"n", "m", "r", "p", "q"}]}`` (p / q the
+        element offsets of the tensor's ``[n, r]`` / ``[m, r]`` factor in the P / Q memory).
+        Slots: 0 = the gradients, 1 = the error memory.  Not capturable (it uploads the task
+        tables)."""
+        if len(rows) != self.n:
+            raise ValueError(f"plan has {self.n} tensors, got {len(rows)} row counts")
+        if not 1 <= int(rank) <= 8:
+            raise ValueError(f"PowerSGD rank must be 1..8, got {rank}")
+        out = (ctypes.c_int64 * max(1, 5 * self.n))()
+        totals = (ctypes.c_int64 * 2)()
+        L.check(L.lib().gs_psgd_layout(self.handle, L.i64_array([int(r) for r in rows]), int(rank), out, totals),
+                "gs_psgd_layout")
+        keys = ("n", "m", "r", "p", "q")
+        self._psgd = {"p_total": int(totals[0]), "q_total": int(totals[1]),
+                      "tensors": [dict(zip(keys, (int(out[5 * t + k]) for k in range(5)))) for t in range(self.n)]}
+        return self._psgd
+
+    def _psgd_mem(self, t: torch.Tensor):
+        if t.dtype != torch.float32 or not t.is_contiguous() or not self._where_plan(t):
+            raise ValueError("PowerSGD factor memory: contiguous fp32 where the plan runs")
+        return t.data_ptr(), t.numel()
+
+    def psgd_orthogonalize(self, which: int, mem: torch.Tensor, eps: float = 0.0, stream=None):
+        """torch's modified Gram-Schmidt on every ``[rows, r]`` factor of the P (``which`` 0)
+        or the Q (1) memory, one launch (gs_psgd_orthogonalize)."""
+        ptr, n = self._psgd_mem(mem)
+        L.check(L.lib().gs_psgd_orthogonalize(self.handle, int(which), ptr, n, float(eps), self._stream(stream)),
+                "gs_psgd_orthogonalize")
+
+    def psgd_project(self, use_error: bool, p: torch.Tensor, q: torch.Tensor, stream=None):
+        """E = M + E (or E = M), P = E·Q: slot 1 holds M' afterwards, slot 0 is only read
+        (gs_psgd_project)."""
+        (pp, pn), (qp, qn) = self._psgd_mem(p), self._psgd_mem(q)
+        L.check(L.lib().gs_psgd_project(self.handle, int(bool(use_error)), pp, pn, qp, qn, self._stream(stream)),
+                "gs_psgd_project")
+
+    def psgd_backproject(self, p: torch.Tensor, q: torch.Tensor, stream=None):
+        """Q = Eᵀ·P in a fixed order, no atomics (gs_psgd_backproject)."""
+        (pp, pn), (qp, qn) = self._psgd_mem(p), self._psgd_mem(q)
+        L.check(L.lib().gs_psgd_backproject(self.handle, pp, pn, qp, qn, self._stream(stream)), "gs_psgd_backproject")
+
+    def psgd_reconstruct(self, p: torch.Tensor, q: torch.Tensor, inv_ws: float = 1.0, stream=None):
+        """Q *= inv_ws (stored), slot 0 = P·Qᵀ, E -= P·Qᵀ (gs_psgd_reconstruct)."""
+        (pp, pn), (qp, qn) = self._psgd_mem(p), self._psgd_mem(q)
+        L.check(L.lib().gs_psgd_reconstruct(self.handle, pp, pn, qp, qn, float(inv_ws), self._stream(stream)),
+                "gs_psgd_reconstruct")
+
     # ------------------------------------------------------------------- EMA
     def ema(self, src_dtype, weight=0.0, copy=False, lowp_dtype=None, stream=None):
         """The weight average on slots 0 = average (fp32), 1 = source (``src_dtype``):

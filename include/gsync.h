@@ -215,6 +215,10 @@ int64_t gs_plan_task_units(gs_plan* p);
 #define GS_OP_MUON_POLY 16
 #define GS_OP_MUON_APPLY 17
 #define GS_OP_MUON_UPDATE 18
+#define GS_OP_PSGD_ORTH 19
+#define GS_OP_PSGD_PROJECT 20
+#define GS_OP_PSGD_BACKPROJECT 21 /* gs_psgd_backproject: the partial pass and its fold, one record each */
+#define GS_OP_PSGD_RECONSTRUCT 22
 int gs_plan_timer_enable(gs_plan* p, int n_slots);
 int gs_plan_timer_read(gs_plan* p, float* ms_out, int32_t* kind_out, int cap);
 /* register the per-tensor pointers of one slot (uploads on change, ordered on `stream`) */
@@ -575,6 +579,56 @@ int gs_muon_apply(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double a, vo
 /* adjust: 0 = "original", 1 = "match_rms_adamw" */
 int gs_muon_update(gs_plan* p, void* ws, int64_t ws_elems, int xsel, double lr, double weight_decay, int adjust,
                    void* stream);
+
+/* PowerSGD (Vogels et al. 2019; torch's powerSGD_hook): rank-r gradient compression, r <= 8.
+ * One plan holds the compressed tensors of a bucket; every stage is ONE grouped launch over
+ * the whole list (gs_psgd_backproject is two), so a bucket's compression is 6 launches
+ * whatever the number of tensors:
+ *   gs_psgd_orthogonalize(Q), gs_psgd_project, [all-reduce P], gs_psgd_orthogonalize(P),
+ *   gs_psgd_backproject, [all-reduce Q], gs_psgd_reconstruct.
+ *
+ * Tensor t is the row-major [n, m] matrix M in memory (n = rows[t] of gs_psgd_layout,
+ * m = numel/n), r = min(n, m, rank).  Slots: 0 = the gradient (f32, inside the bucket),
+ * 1 = E (f32), the error-feedback memory and the stages' working copy of M' = M + E.
+ * P [n, r] and Q [m, r] are row-major in the caller's two fp32 buffers at the offsets
+ * gs_psgd_layout reports: tensors in plan order, n*r / m*r elements each, no padding.
+ * Arithmetic, per tensor.  Operands and every stored value are fp32; every sum of products
+ * (P, Q, G, the Gram-Schmidt sums) is accumulated in fp64, where fp32 products are exact,
+ * and rounded to fp32 once where it is stored — the passes are bound by memory:
+ *   orthogonalize(X = P or Q, eps), modified Gram-Schmidt, for i = 0..r-1:
+ *       c_i = c_i / (sqrt(Σc_i²) + eps)              an IEEE division per element
+ *       c_j = c_j - (Σ c_i·c_j) * c_i   for j > i    all j from the same sweep over c_i
+ *       (a factor with r = rows is square: its last columns amplify a dot product's rounding)
+ *   project(use_error):  E = use_error ? M + E : M;  P = E·Q        (slot 0 is not written)
+ *   backproject:         Q = Eᵀ·P
+ *   reconstruct(inv_ws): Q = Q * inv_ws (stored);  G = P·Qᵀ (slot 0);  E = E - G
+ *       (G's r products can cancel: E = M' - P·Qᵀ still holds to one rounding each)
+ * The stored values are torch's (add_, bmm, bmm, div_, bmm, the subtraction), each closer
+ * to exact than an fp32 accumulation leaves it; torch takes the rank > 2
+ * orthogonalisation through a QR factorisation in fp32.
+ * The order inside a sum is the kernel's own and fixed by the layout alone: project
+ * adds a row's 4-column lane groups by a fixed lane tree, 1024-column slabs in ascending
+ * order; backproject adds rows w, w+4, .. of a 128-row block per wave, the 4 waves in
+ * order, the row blocks in order (a second launch); the Gram-Schmidt sums add rows k,
+ * k+256, .. per thread, then the wave tree, then the 4 waves in order.  No atomics: the
+ * device result is bit-reproducible run to run.  As for Muon, host and device agree to
+ * the accumulation order only (the host adds in ascending index order).
+ *
+ * gs_psgd_layout fixes it: layout_out[5t..5t+4] = n, m, r and the element offsets of P_t
+ * and Q_t; totals_out[0..1] = the elements of the P and the Q memory.  On a HIP plan it
+ * uploads the task tables and allocates backproject's scratch (synchronous: not capturable).
+ * p_elems / q_elems are checked against the layout's totals.
+ * replaces: T:distributed/algorithms/ddp_comm_hooks/powerSGD_hook.py:405-650 (per bucket an
+ *           add_, a clone, per tensor 3 bmm and a Python loop of ~3 launches per column
+ *           pair in _orthogonalize_gram_schmidt, a device synchronize, the subtraction) */
+int gs_psgd_layout(gs_plan* p, const int64_t* rows, int rank, int64_t* layout_out, int64_t* totals_out);
+/* which: 0 = P, 1 = Q; mem: that factor memory */
+int gs_psgd_orthogonalize(gs_plan* p, int which, float* mem, int64_t mem_elems, double eps, void* stream);
+int gs_psgd_project(gs_plan* p, int use_error, float* pmem, int64_t p_elems, const float* qmem, int64_t q_elems,
+                    void* stream);
+int gs_psgd_backproject(gs_plan* p, const float* pmem, int64_t p_elems, float* qmem, int64_t q_elems, void* stream);
+int gs_psgd_reconstruct(gs_plan* p, const float* pmem, int64_t p_elems, float* qmem, int64_t q_elems, double inv_ws,
+                        void* stream);
 
 /* EMA / SWA weight averaging: one pass a' = lerp(a, s, w) over a whole model.
  * Slots: 0 = the average a (f32), 1 = the source s (src_dtype: f32, bf16 or f16, converted
