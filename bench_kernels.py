@@ -93,6 +93,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--skip-torch", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated row-name prefixes to run (default: all rows)")
+    ap.add_argument("--quant-torch-elems", type=int, default=0,
+                    help="quant rows: elements torch's per-channel hook is timed at (0: the whole bucket)")
     ap.add_argument("--tag", default=os.environ.get("GSYNC_LIB", "libgsync").split("/")[-1])
     args = ap.parse_args()
     from distributed_training_amd.multi_tensor import TensorListPlan
@@ -510,6 +512,8 @@ def main():
     if want("psgd"):
         for rank in (1, 4):
             psgd_row(args, dev, rank)
+    if want("quant"):
+        quant_rows(args, dev, torch_numel=args.quant_torch_elems or None)
 
 
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X dense bf16 matrix peak (AMD's data sheet: 2.5 PFLOP/s)
@@ -624,6 +628,69 @@ def psgd_row(args, dev, rank, repeats=5):
            "fused_frac_of_8TBps": 7 * 4 * comp / (med(times["fused"]) * 1e-3) / 1e9 / HBM_PEAK,
            "speedup": med(times["torch"]) / med(times["fused"])}
     print(json.dumps(row), flush=True)
+
+
+def quant_rows(args, dev, n=(25 << 20) // 4, repeats=5, torch_numel=None):
+    """The uint8 quantization kernels on one 25 MiB bucket (a ResNet-50 DDP bucket), each between its own
+    pair of device events: achieved HBM rate over the bytes the algorithm moves (quantize: 4 read + 1 written
+    per element, the per-tensor form reads the bucket twice; dequant-mean: ws read + 4 written).  Then each
+    hook's per-bucket time at world size 1 against torch's own hook on the same GPU, alternating, `repeats`
+    windows each after a warm-up: median, minimum and maximum.  torch's hooks index their all-gather's
+    future as [one stacked tensor]; the outputs are stacked for them here (part of torch's time, one small
+    copy).  `torch_numel`: torch's per-channel hook loops over the channels in Python; it is timed at this
+    many elements when the whole bucket would not fit the run (None: the whole bucket)."""
+    import types
+
+    import torch.distributed as dist
+    from torch.distributed.algorithms.ddp_comm_hooks import quantization_hooks as TQ
+
+    import distributed_training_amd as D
+    from distributed_training_amd.multi_tensor import QuantPlan
+
+    if not dist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29531")
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    g = torch.Generator(device=dev).manual_seed(3)
+    src = torch.randn(n, device=dev, generator=g) * 0.01
+    buf, plan = src.clone(), QuantPlan(dev)
+    pay = {bs: torch.zeros(plan.payload_bytes(n, bs), dtype=torch.uint8, device=dev) for bs in (0, 512)}
+    for name, nbytes, fn in (("quant_perchannel_512", 5 * n, lambda: plan.quant_perchannel(src, pay[512], 512)),
+                             ("quant_pertensor", 9 * n, lambda: plan.quant_pertensor(src, pay[0])),
+                             ("dequant_mean_ws1", 5 * n, lambda: plan.dequant_mean(pay[512], 1, buf, 512))):
+        med, avg = timeit(fn, args.iters)
+        _LAST.pop("fn", None)
+        gbs = nbytes / (med * 1e-3) / 1e9
+        print(json.dumps({"kernel": name, "impl": "libgsync", "elems": n, "tag": args.tag, "alg_bytes": nbytes,
+                          "median_ms": med, "avg_ms": avg, "GBps": gbs, "frac_of_8TBps": gbs / HBM_PEAK}), flush=True)
+
+    def stacked_all_gather(outs, t, group=None, async_op=True):
+        fut = dist.all_gather(outs, t, group=group, async_op=True).get_future().then(lambda _: [torch.stack(outs)])
+        return types.SimpleNamespace(get_future=lambda: fut)
+
+    TQ.dist = types.SimpleNamespace(group=dist.group, get_rank=dist.get_rank, all_gather=stacked_all_gather)
+    med = lambda ts: sorted(ts)[len(ts) // 2]  # noqa: E731
+    for name, ours, theirs, tn in (
+            ("quant_pertensor_hook", D.quantization_pertensor_hook, TQ.quantization_pertensor_hook, n),
+            ("quant_perchannel_hook", D.quantization_perchannel_hook, TQ.quantization_perchannel_hook,
+             torch_numel or n)):
+        sides = {"fused": (ours, D.GradBucket(0, src.clone(), [], [], True), args.iters),
+                 "torch": (theirs, D.GradBucket(0, src[:tn].clone(), [], [], True), 1 if "channel" in name else 5)}
+        times = {k: [] for k in sides}
+        if args.skip_torch:
+            del sides["torch"]
+        for _ in range(repeats):
+            for side, (hook, bucket, iters) in sides.items():
+                hook(None, bucket).wait()
+                torch.cuda.synchronize()
+                times[side].append(timeit_batched(lambda: hook(None, bucket).wait(), iters))
+        row = {"kernel": name, "elems": n, "tag": args.tag, "fused_ms": med(times["fused"]),
+               "fused_ms_min_max": [min(times["fused"]), max(times["fused"])], "fused_launches": 3 + ("tensor" in name)}
+        if times["torch"]:
+            row.update({"torch_elems": tn, "torch_ms": med(times["torch"]),
+                        "torch_ms_min_max": [min(times["torch"]), max(times["torch"])],
+                        **({"speedup": med(times["torch"]) / med(times["fused"])} if tn == n else {})})
+        print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,8 @@ Public surface:
   FusedSGD / FusedAdam / FusedAdamW / FusedLARS / FusedLAMB / FusedMuon / clip_grad_norm_
   Communicator              libgsync-owned RCCL communicator
   PowerSGDState / powerSGD_hook  torch's PowerSGD gradient-compression comm hook on grouped HIP kernels
+  quantization_pertensor_hook / quantization_perchannel_hook  torch's uint8 gradient-quantization comm
+                            hooks: three launches and one all-gather per bucket, torch's bits
   CapturedStep              the whole training step recorded into one hipGraph
   AveragedModel / ShardedAveragedModel / get_ema_multi_avg_fn / get_swa_multi_avg_fn
                             fused EMA / SWA weight averaging (torch.optim.swa_utils drop-ins)
@@ -23,7 +25,8 @@ Public surface:
 from . import _lib  # noqa: F401
 from .comm import Communicator, destroy_communicators, get_communicator  # noqa: F401
 from .ddp import DDP, DistributedDataParallel, GradBucket, compute_bucket_assignment_by_size  # noqa: F401
-from .comm_hooks import PowerSGDState, powerSGD_hook  # noqa: F401
+from .comm_hooks import (PowerSGDState, powerSGD_hook, quantization_perchannel_hook,  # noqa: F401
+                         quantization_pertensor_hook)
 from .graphs import CapturedStep  # noqa: F401
 from .ema import AveragedModel, ShardedAveragedModel, get_ema_multi_avg_fn, get_swa_multi_avg_fn  # noqa: F401
 from .data import MixedTarget, MixUpCutMix, RandomResizedCropFlip, ResizeCenterCrop  # noqa: F401

@@ -13,6 +13,11 @@ orthogonalisation, a clone of the bucket and a device synchronize per bucket.  H
 bucket is 6 grouped launches over all its compressed tensors (``gs_psgd_*``,
 include/gsync.h) plus one pack and one unpack for the rest, in stream order on the stream
 the hook is called on, with no host synchronisation and no device-to-host read.
+
+``quantization_pertensor_hook`` / ``quantization_perchannel_hook`` are drop-ins for torch's
+uint8 quantization hooks (T:distributed/algorithms/ddp_comm_hooks/quantization_hooks.py),
+with torch's results bit for bit: three launches (``gs_quant_*``, ``gs_dequant_mean``) and
+one all-gather per bucket.
 """
 from __future__ import annotations
 
@@ -23,7 +28,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .multi_tensor import TensorListPlan, is_dense
+from .multi_tensor import QuantPlan, TensorListPlan, is_dense
 
 logger = logging.getLogger(__name__)
 
@@ -300,3 +305,84 @@ def powerSGD_hook(state: PowerSGDState, bucket) -> torch.futures.Future:
 
     state.maybe_increase_iter(bucket)
     return _future(buf)
+
+
+# ---------------------------------------------------------------------- uint8 quantization
+# (group, bucket index, buffer address, numel, bucket_size) -> (launches, payload, receive
+# buffer): a changed layout simply makes a new entry
+_QUANT_CACHE: dict = {}
+
+
+def _all_gather_bytes(group, send: torch.Tensor, recv: torch.Tensor, ws: int):
+    """``recv`` = every rank's ``send`` back to back, ordered on the current stream; the
+    transports are :func:`_all_reduce_sum`'s."""
+    if send.is_cuda and _backend(group) in ("nccl", "rccl"):
+        from .comm import get_communicator
+
+        pg = None if group is None or group is dist.group.WORLD else group
+        get_communicator(pg, send.device).all_gather(send, recv, stream=L.stream_ptr(send.device))
+    elif send.is_cuda:
+        host = torch.empty(recv.numel(), dtype=torch.uint8)
+        dist.all_gather(list(host.view(ws, -1).unbind(0)), send.to("cpu"), group=group)
+        recv.copy_(host)
+    else:
+        dist.all_gather(list(recv.view(ws, -1).unbind(0)), send, group=group)
+
+
+def _quantization_hook(name, process_group, bucket, bucket_size):
+    buf = bucket.buffer()
+    if buf.dtype != torch.float32:
+        raise ValueError(f"{name} supports fp32 bucket buffers only, got {buf.dtype}")
+    if bucket_size and not (16 <= bucket_size <= 4096 and bucket_size % 16 == 0):
+        raise ValueError(f"{name} supports a bucket_size that is a multiple of 16 in 16..4096, got {bucket_size}")
+    group = process_group if process_group is not None else dist.group.WORLD
+    ws = dist.get_world_size(group)
+    key = (id(group), ws, bucket.index(), buf.data_ptr(), buf.numel(), bucket_size)
+    ctx = _QUANT_CACHE.get(key)
+    if ctx is None:
+        nbytes = QuantPlan.payload_bytes(buf.numel(), bucket_size)
+        ctx = _QUANT_CACHE[key] = (QuantPlan(buf.device), torch.zeros(nbytes, dtype=torch.uint8, device=buf.device),
+                                   torch.zeros(ws * nbytes, dtype=torch.uint8, device=buf.device))
+    plan, payload, gathered = ctx
+    if buf.numel():
+        if bucket_size:
+            plan.quant_perchannel(buf, payload, bucket_size)
+        else:
+            plan.quant_pertensor(buf, payload)
+        _all_gather_bytes(group, payload, gathered, ws)
+        plan.dequant_mean(gathered, ws, buf, bucket_size)
+    return _future(buf)
+
+
+def quantization_pertensor_hook(process_group, bucket) -> torch.futures.Future:
+    """torch's ``quantization_pertensor_hook``
+    (T:distributed/algorithms/ddp_comm_hooks/quantization_hooks.py) on libgsync's kernels,
+    registered the same way (``ddp.register_comm_hook(process_group, quantization_pertensor_hook)``):
+    the bucket travels as uint8 with one MinMaxObserver ``(scale, zero point)`` per rank, and
+    comes back as the mean of all ranks' dequantized buckets, written in place.
+
+    The arithmetic is torch's, bit for bit in fp32 (``gs_quant_pertensor``, ``gs_dequant_mean``
+    in include/gsync.h).  Per bucket: a min/max pass, a quantize pass, ONE all-gather of a
+    payload that carries the bytes and the qparams (torch: two all-gathers, an observer module
+    and ``ws`` dequantize-and-add temporaries), one dequantize-and-average launch; in stream
+    order on the calling stream, with no host synchronisation over RCCL.  Over gloo a device
+    payload is staged through host memory; CPU buckets run on the host backend.  A value that
+    is not finite anywhere makes the whole bucket NaN on every rank.  fp32 buckets only."""
+    return _quantization_hook("quantization_pertensor_hook", process_group, bucket, 0)
+
+
+def quantization_perchannel_hook(process_group, bucket, bucket_size=512) -> torch.futures.Future:
+    """torch's ``quantization_perchannel_hook`` on libgsync's kernels: as
+    :func:`quantization_pertensor_hook`, with one ``(scale, zero point)`` per channel of
+    ``bucket_size`` consecutive elements of the flat bucket (``functools.partial(
+    quantization_perchannel_hook, bucket_size=128)`` as with torch's).  One quantize launch
+    (``gs_quant_perchannel``: a channel is read once and stays in registers between its
+    min/max and its quantization), one all-gather, one dequantize-and-average launch, where
+    torch loops over the channels in Python twice.  A channel that holds a value that is not
+    finite comes out NaN on every rank; the others are unaffected.  ``bucket_size``: a
+    multiple of 16 in 16..4096 (``ValueError`` otherwise); torch's extra all-zero channel
+    when the bucket is a multiple of ``bucket_size`` is not sent."""
+    if not bucket_size:
+        raise ValueError(f"quantization_perchannel_hook supports a bucket_size that is a multiple of 16 in 16..4096, "
+                         f"got {bucket_size}")
+    return _quantization_hook("quantization_perchannel_hook", process_group, bucket, int(bucket_size))

@@ -666,6 +666,20 @@ int host_psgd_orthogonalize(gs_plan* p, int which, float* mem, float eps);
 int host_psgd_project(gs_plan* p, int use_error, float* pmem, const float* qmem);
 int host_psgd_backproject(gs_plan* p, const float* pmem, float* qmem);
 int host_psgd_reconstruct(gs_plan* p, const float* pmem, float* qmem, float inv_ws);
+// ---- uint8 quantization (gs_quant_*: gs_quant_kernels.hip / gs_host.cpp) ----
+// A payload's geometry: C channels, Q bytes of quantized values, then the scales and zero points.
+struct QuantLayout {
+  int64_t C, Q;
+  int64_t bytes() const { return Q + 8 * C; }
+};
+inline QuantLayout quant_layout(int64_t n, int bucket_size) {
+  QuantLayout l;
+  l.C = bucket_size ? (n + bucket_size - 1) / bucket_size : 1;
+  l.Q = ((bucket_size ? l.C * bucket_size : n) + 15) & ~int64_t(15);
+  return l;
+}
+int host_quant(const float* x, int64_t n, int bucket_size, void* payload);  // bucket_size 0: per tensor
+int host_dequant_mean(const void* gathered, int world_size, float* out, int64_t n, int bucket_size);
 int hip_device_count();
 int hip_memset_async(void* dst, int value, size_t bytes, void* stream);
 int hip_stream_wait(void* waiter, void* signaler);

@@ -861,6 +861,48 @@ int host_xent_mix_bwd(const void* logits, int dt, const int64_t* labels, const i
   return GS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// gs_quant_perchannel / gs_quant_pertensor / gs_dequant_mean on the host: the rules of
+// include/gsync.h channel by channel, on gs_math.h's per-element functions.
+int host_quant(const float* x, int64_t n, int bucket_size, void* payload) {
+  const QuantLayout l = quant_layout(n, bucket_size);
+  uint8_t* q = static_cast<uint8_t*>(payload);
+  float* scales = reinterpret_cast<float*>(q + l.Q);
+  int32_t* zps = reinterpret_cast<int32_t*>(q + l.Q + 4 * l.C);
+  const int64_t width = bucket_size ? bucket_size : n;
+  for (int64_t c = 0; c < l.C; ++c) {
+    const int64_t e0 = c * width, e1 = std::min(n, e0 + width);
+    float lo = 0.f, hi = 0.f;
+    for (int64_t e = e0; e < e1; ++e) quant_fold(x[e], &lo, &hi);
+    const QuantParams qp = quant_params(lo, hi);
+    const float zpf = static_cast<float>(qp.zp);
+    for (int64_t e = e0; e < e1; ++e) q[e] = static_cast<uint8_t>(quant_value(x[e], qp.scale, zpf));
+    for (int64_t e = e1; e < e0 + width; ++e) q[e] = static_cast<uint8_t>(quant_value(0.f, qp.scale, zpf));
+    scales[c] = qp.scale;
+    zps[c] = qp.zp;
+  }
+  return GS_OK;
+}
+
+int host_dequant_mean(const void* gathered, int world_size, float* out, int64_t n, int bucket_size) {
+  const QuantLayout l = quant_layout(n, bucket_size);
+  const uint8_t* g = static_cast<const uint8_t*>(gathered);
+  const float d = static_cast<float>(world_size);
+  for (int64_t e = 0; e < n; ++e) {
+    const int64_t c = bucket_size ? e / bucket_size : 0;
+    float a = 0.f;
+    for (int r = 0; r < world_size; ++r) {
+      const uint8_t* p = g + r * l.bytes();
+      const float scale = reinterpret_cast<const float*>(p + l.Q)[c];
+      const float zpf = static_cast<float>(reinterpret_cast<const int32_t*>(p + l.Q + 4 * l.C)[c]);
+      const float t = dequant_value(p[e], scale, zpf);
+      a = r ? a + t : t;
+    }
+    out[e] = a / d;
+  }
+  return GS_OK;
+}
+
 }  // namespace gs
 
 extern "C" int gs_set_host_threads(int n) {

@@ -291,4 +291,44 @@ GS_HD_INL float clip_factor(const ClipArgs& c, const float* gscale, float* sq, f
   return coef * c.coef_mul;
 }
 
+// ---------------------------------------------------------------- uint8 quantization (gs_quant_*)
+// torch's MinMaxObserver qparams and quantize / dequantize in fp32
+// (T:ao/quantization/observer.py _calculate_qparams, quint8 affine;
+// T:distributed/algorithms/ddp_comm_hooks/quantization_hooks.py), every step one correctly
+// rounded operation: both divisions are true divisions and nothing is fused.
+struct QuantParams {
+  float scale;
+  int32_t zp;
+};
+// one value folded into a channel's running (lo, hi), which start at 0: a value that is not
+// finite opens the range to (-inf, +inf), which quant_params turns into a NaN scale
+GS_HD_INL void quant_fold(float v, float* lo, float* hi) {
+  if (!(v - v == 0.f)) {
+    *lo = -INFINITY;
+    *hi = INFINITY;
+  }
+  *lo = fminf(*lo, v);
+  *hi = fmaxf(*hi, v);
+}
+// lo = min(min x, 0), hi = max(max x, 0)
+GS_HD_INL QuantParams quant_params(float lo, float hi) {
+  QuantParams q;
+  if (!(lo > -INFINITY && hi < INFINITY)) {
+    q.scale = NAN;
+    q.zp = 0;
+    return q;
+  }
+  const float s = (hi - lo) / 255.0f;
+  q.scale = s > 1.1920928955078125e-07f ? s : 1.1920928955078125e-07f;  // FLT_EPSILON
+  const int z = 0 - static_cast<int>(rintf(lo / q.scale));
+  q.zp = z < 0 ? 0 : (z > 255 ? 255 : z);
+  return q;
+}
+// the byte of x; zpf = (float)zp.  A NaN (a NaN scale) becomes 0.
+GS_HD_INL uint32_t quant_value(float x, float scale, float zpf) {
+  const float y = rintf(x / scale) + zpf;
+  return static_cast<uint32_t>(fminf(fmaxf(y, 0.f), 255.f));
+}
+GS_HD_INL float dequant_value(uint32_t q, float scale, float zpf) { return scale * (static_cast<float>(q) - zpf); }
+
 }  // namespace gs

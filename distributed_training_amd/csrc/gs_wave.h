@@ -1,5 +1,5 @@
 // Device helpers shared by the one-wavefront-per-row kernels (gs_eval_kernels.hip,
-// gs_loss_kernels.hip): a logit load by dtype, the wave-64 butterflies and the per-lane
+// gs_loss_kernels.hip, gs_quant_kernels.hip): a logit load by dtype, the wave-64 butterflies and the per-lane
 // balanced tree of partial sums.  HIP translation units only.
 #pragma once
 
@@ -27,6 +27,21 @@ __device__ __forceinline__ float ld_logit(const void* base, int64_t i) {
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
+  return v;
+}
+// min / max over the aligned group of `width` lanes a lane belongs to (a wave-uniform power of
+// two <= 64): the butterfly's steps below the width, so every lane of a group ends with the
+// group's value.  All 64 lanes must be active.
+__device__ __forceinline__ float seg_min(float v, int width) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1)
+    if (o < width) v = fminf(v, __shfl_xor(v, o, kWave));
+  return v;
+}
+__device__ __forceinline__ float seg_max(float v, int width) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1)
+    if (o < width) v = fmaxf(v, __shfl_xor(v, o, kWave));
   return v;
 }
 __device__ __forceinline__ float wave_sum(float v) {

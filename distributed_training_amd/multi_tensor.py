@@ -10,6 +10,7 @@ gradient-sync path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import Sequence
 
@@ -496,6 +497,50 @@ class TensorListPlan:
                 None if found_inf is None else found_inf.data_ptr(), self._stream(stream)),
             "gs_adam_step",
         )
+
+
+class QuantPlan:
+    """The launches of the uint8 quantization comm hooks on one device (``gs_quant_*`` /
+    ``gs_dequant_mean``, include/gsync.h): no tensor list, only the per-tensor form's scratch
+    of (lo, hi) pairs.  A payload is ``payload_bytes(n, bucket_size)`` bytes of uint8: the
+    quantized values (rounded up to 16 bytes), the channels' fp32 scales, their int32 zero
+    points; ``bucket_size`` 0 is the per-tensor form."""
+
+    def __init__(self, device: torch.device):
+        self.device = torch.device(device)
+        self.kind = L.GS_DEV_HIP if self.device.type == "cuda" else L.GS_DEV_HOST
+        self._scratch = None
+
+    @staticmethod
+    def payload_bytes(n: int, bucket_size: int = 0) -> int:
+        return L.check(L.lib().gs_quant_payload_bytes(int(n), int(bucket_size)), "gs_quant_payload_bytes")
+
+    def _call(self, name, buf: torch.Tensor, wire: torch.Tensor, *args):
+        if buf.dtype != torch.float32 or wire.dtype != torch.uint8 or not buf.is_contiguous() or \
+                not wire.is_contiguous() or buf.device != self.device or wire.device != self.device:
+            raise ValueError("quantization: a contiguous fp32 bucket and a contiguous uint8 payload on the plan's device")
+        with torch.cuda.device(self.device) if self.kind == L.GS_DEV_HIP else contextlib.nullcontext():
+            L.check(getattr(L.lib(), name)(self.kind, *args, L.stream_ptr(self.device)), name)
+
+    def quant_perchannel(self, buf: torch.Tensor, payload: torch.Tensor, bucket_size: int):
+        """payload = the bytes, scales and zero points of ``buf`` in channels of ``bucket_size``
+        elements, one launch (gs_quant_perchannel)."""
+        self._call("gs_quant_perchannel", buf, payload, buf.data_ptr(), buf.numel(), int(bucket_size),
+                   payload.data_ptr(), payload.numel())
+
+    def quant_pertensor(self, buf: torch.Tensor, payload: torch.Tensor):
+        """payload = the bytes, scale and zero point of ``buf`` as one channel: a min/max
+        pass and a quantize pass (gs_quant_pertensor)."""
+        if self._scratch is None and self.kind == L.GS_DEV_HIP:
+            self._scratch = torch.empty(2 * L.GS_QUANT_PARTIALS, dtype=torch.float32, device=self.device)
+        self._call("gs_quant_pertensor", buf, payload, buf.data_ptr(), buf.numel(), payload.data_ptr(), payload.numel(),
+                   None if self._scratch is None else self._scratch.data_ptr())
+
+    def dequant_mean(self, gathered: torch.Tensor, ws: int, buf: torch.Tensor, bucket_size: int = 0):
+        """buf = the mean of the ``ws`` payloads' dequantized values, added in rank order and
+        divided by ``ws``, one launch (gs_dequant_mean)."""
+        self._call("gs_dequant_mean", buf, gathered, gathered.data_ptr(), gathered.numel(), int(ws), buf.data_ptr(),
+                   buf.numel(), int(bucket_size))
 
 
 def clip_coef(sqnorm: torch.Tensor, max_norm: float, eps: float, coef: torch.Tensor,

@@ -1117,6 +1117,53 @@ int gs_xent_mix_bwd(int device_kind, const void* logits, int logits_dtype, const
                     int64_t ignore_index, float label_smoothing, int reduction, const void* rows, const void* red,
                     const float* grad_out, void* dlogits, int64_t d_row_stride, void* stream);
 
+/* ======================================================================
+ * uint8 gradient quantization for the all-gather comm hooks
+ * (csrc/gs_quant_kernels.hip; Python: distributed_training_amd/comm_hooks.py)
+ * replaces: T:distributed/algorithms/ddp_comm_hooks/quantization_hooks.py — per bucket a
+ *           MinMaxObserver / PerChannelMinMaxObserver module, two all-gathers, a Python loop
+ *           over every channel (twice) and a world-size loop of dequantize-and-add temporaries
+ * ==================================================================== */
+/* A bucket x of n fp32 elements is cut into C = ceil(n / bucket_size) channels of bucket_size
+ * consecutive elements (the per-tensor form: one channel, the whole bucket; bucket_size 0
+ * names it below).  For a channel, in fp32, every step one correctly rounded operation:
+ *   lo = min(min x, 0)   hi = max(max x, 0)      (elements past n count as zeros)
+ *   scale = max((hi - lo) / 255.0f, FLT_EPSILON)
+ *   zp    = clamp(0 - (int)rintf(lo / scale), 0, 255)
+ *   q     = (uint8)clamp(rintf(x / scale) + zp, 0, 255)
+ * which are torch's MinMaxObserver qparams and its quantize.  A channel that holds a value
+ * that is not finite gets scale = NaN, zp = 0, so every element of it dequantizes to NaN.
+ * A rank's payload, one contiguous block for one all-gather:
+ *   Q = C * bucket_size (per-tensor: n) rounded up to 16 bytes of quantized values,
+ *   then C fp32 scales, then C int32 zero points:  Q + 8 * C bytes
+ * gs_quant_payload_bytes returns that size, or GS_EINVAL for n < 0 or n > GS_QUANT_MAX_NUMEL or
+ * a bucket_size that is neither 0 nor a multiple of 16 in 16..4096. */
+#define GS_QUANT_MAX_NUMEL ((int64_t)1 << 34)
+#define GS_QUANT_PARTIALS 1024 /* gs_quant_pertensor: the (lo, hi) pairs of its scratch */
+int64_t gs_quant_payload_bytes(int64_t n, int bucket_size);
+/* The payload of x, per channel.  x: fp32 [n], 4-byte aligned; payload: payload_bytes >=
+ * gs_quant_payload_bytes(n, bucket_size), 16-byte aligned; both live where device_kind says.
+ * GS_DEV_HIP: one launch on `stream`; a channel's values are read once and stay in registers
+ * between the min/max and the quantization.  The bytes of the last channel past n are
+ * written (the bytes of zeros); x is not read past n.  n == 0 is a no-op. */
+int gs_quant_perchannel(int device_kind, const float* x, int64_t n, int bucket_size, void* payload,
+                        int64_t payload_bytes, void* stream);
+/* The payload of x as one channel.  scratch: 8 * GS_QUANT_PARTIALS bytes, 8-byte aligned,
+ * beside x (GS_DEV_HIP; may be NULL on the host).  GS_DEV_HIP: two launches, a min/max pass
+ * that leaves one (lo, hi) pair per workgroup in scratch and a quantize pass whose every
+ * workgroup folds those pairs itself; no atomics, nothing read back. */
+int gs_quant_pertensor(int device_kind, const float* x, int64_t n, void* payload, int64_t payload_bytes,
+                       void* scratch, void* stream);
+/* out[i] = (sum over ranks r = 0 .. world_size - 1, in that order, starting from rank 0's
+ * term, of scale_r * ((float)q_r[i] - (float)zp_r)) / (float)world_size for i < n, every
+ * multiply, add and the final division rounded once (no fma, no reciprocal): the mean of the
+ * dequantized buckets.  gathered: world_size payloads of (n, bucket_size) back to back
+ * (gathered_bytes >= world_size * gs_quant_payload_bytes), 8-byte aligned; out: fp32 [n],
+ * 4-byte aligned, not overlapping gathered.  bucket_size 0: per-tensor payloads.
+ * GS_DEV_HIP: one launch. */
+int gs_dequant_mean(int device_kind, const void* gathered, int64_t gathered_bytes, int world_size, float* out,
+                    int64_t n, int bucket_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
