@@ -509,6 +509,8 @@ def main():
         rec("adam", 28 * n, *timeit(fadam.step, args.iters), "torch.optim.Adam fused")
     if want("muon"):
         muon_row(args, dev, shapes)
+    if want("adafactor"):
+        adafactor_row(args, dev, shapes)
     if want("psgd"):
         for rank in (1, 4):
             psgd_row(args, dev, rank)
@@ -559,6 +561,57 @@ def muon_row(args, dev, shapes, ns_steps=5, repeats=5):
            "ns_gflop": flop / 1e9, "fused_ns_tflops": flop / (med(t_f) * 1e-3) / 1e12,
            "fused_frac_of_bf16_peak": flop / (med(t_f) * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS,
            "speedup": med(t_t) / med(t_f)}
+    print(json.dumps(row), flush=True)
+
+
+def adafactor_row(args, dev, shapes, repeats=5):
+    """FusedAdafactor against torch.optim.Adafactor on the model's parameter list (filters
+    channels_last, as the ResNet configurations run them): both in this process, alternating,
+    each repeat `iters` steps between one pair of device events after a warm-up and a
+    synchronise.  One JSON line: ms per step of both (median over the repeats, and every
+    repeat), the launches per step (fused: the timed launches of one step, counted by the
+    plan's timer; torch: 15 per factored and 9 per vector parameter, its op sequence, plus
+    two host reads each) and the achieved rate over the traffic model — 20 B per element a
+    lane owns (g and p read by the stats pass; g and p read, p written by the update), 24 B
+    per element of a tiled matrix (one more read of g by the row / column sums)."""
+    from distributed_training_amd.optim import FusedAdafactor
+
+    g = torch.Generator(device=dev).manual_seed(1)
+
+    def make(s):
+        x = torch.randn(tuple(s), device=dev, generator=g)
+        return x.contiguous(memory_format=torch.channels_last) if len(s) == 4 else x
+
+    mine = [torch.nn.Parameter(make(s)) for s in shapes]
+    theirs = [torch.nn.Parameter(p.detach().clone()) for p in mine]
+    for p, q in zip(mine, theirs):
+        p.grad = make(p.shape) * 0.01
+        q.grad = p.grad.clone()
+        assert q.stride() == p.stride() and q.grad.stride() == p.stride()
+    fused, ref = FusedAdafactor(mine, lr=1e-6), torch.optim.Adafactor(theirs, lr=1e-6)
+    nbytes = sum(p.numel() * (24 if p.ndim > 1 and p.shape[-1] * p.shape[-2] > 64 else 20) for p in mine)
+
+    def run(opt):
+        for _ in range(3):
+            opt.step()
+        torch.cuda.synchronize()
+        return timeit_batched(opt.step, args.iters)
+
+    t_f, t_t = [], []
+    for _ in range(repeats):
+        t_f.append(run(fused))
+        t_t.append(run(ref))
+    fused.enable_kernel_timer()
+    fused.step()
+    torch.cuda.synchronize()
+    launches = len(fused.kernel_ms())
+    med = lambda ts: sorted(ts)[len(ts) // 2]  # noqa: E731
+    gbs = nbytes / (med(t_f) * 1e-3) / 1e9
+    row = {"kernel": "adafactor_step", "model": args.model, "tensors": len(mine), "tag": args.tag,
+           "fused_ms": med(t_f), "torch_ms": med(t_t), "fused_ms_repeats": t_f, "torch_ms_repeats": t_t,
+           "fused_launches": launches, "torch_launches": sum(15 if p.ndim > 1 else 9 for p in mine),
+           "torch_host_reads": 2 * len(mine), "alg_bytes": nbytes, "fused_GBps": gbs,
+           "fused_frac_of_8TBps": gbs / HBM_PEAK, "speedup": med(t_t) / med(t_f)}
     print(json.dumps(row), flush=True)
 
 

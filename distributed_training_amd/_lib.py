@@ -45,6 +45,7 @@ GS_OP_LAMB_MOMENTS, GS_OP_LAMB = 11, 12
 GS_OP_EMA = 13
 GS_OP_MUON_PREP, GS_OP_MUON_GRAM, GS_OP_MUON_POLY, GS_OP_MUON_APPLY, GS_OP_MUON_UPDATE = 14, 15, 16, 17, 18
 GS_OP_PSGD_ORTH, GS_OP_PSGD_PROJECT, GS_OP_PSGD_BACKPROJECT, GS_OP_PSGD_RECONSTRUCT = 19, 20, 21, 22
+GS_OP_ADAFACTOR_STATS, GS_OP_ADAFACTOR_STEP = 23, 24
 GS_EMA_EMA, GS_EMA_SWA, GS_EMA_WARMUP = 0, 1, 2
 GS_QUANT_PARTIALS = 1024  # gs_quant_pertensor: the (lo, hi) pairs of its scratch
 
@@ -175,6 +176,9 @@ SIGNATURES = {
     "gs_psgd_project": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp, _c_i64, _vp]),
     "gs_psgd_backproject": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _vp]),
     "gs_psgd_reconstruct": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_d, _vp]),
+    "gs_adafactor_layout": (_c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "gs_adafactor_stats": (_c_int, [_vp, _c_d, _c_d, _vp, _vp, _c_i64, _vp]),
+    "gs_adafactor_step": (_c_int, [_vp, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _c_int, _vp, _vp, _c_i64, _vp]),
     "gs_quant_payload_bytes": (_c_i64, [_c_i64, _c_int]),
     "gs_quant_perchannel": (_c_int, [_c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _vp]),
     "gs_quant_pertensor": (_c_int, [_c_int, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),

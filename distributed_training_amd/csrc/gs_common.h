@@ -186,6 +186,55 @@ struct PsgdTables {  // device pointers (HIP plans)
   int32_t orth_lds[2];    // dynamic LDS bytes of the two orthogonalize launches
 };
 
+// ---- Adafactor (gs_adafactor_*: gs_adafactor_kernels.hip / gs_host.cpp) ----
+// Tensor t of the plan is a batch of O x I matrices of R x C elements at element strides
+// (so, si, sr, sc); its factors are slots 2 (row_var [O, I, R], or the variance of a vector)
+// and 3 (col_var [O, I, C]), contiguous.  A regime per tensor:
+//   kAfLane    R * C <= kAfLaneElems: a lane owns a matrix and reads it where it lies
+//   kAfStaged  the same for a contiguous batch of a shape in af_shape_id's list: the workgroup's
+//              matrices come through LDS
+//   kAfTiled   R * C > kAfLaneElems (sc == 1): kAfTileRows x kAfTileCols tiles
+constexpr int kAfLaneElems = 64;
+constexpr int kAfTileRows = 64;    // 4 waves x 16 rows
+constexpr int kAfTileCols = 256;   // 64 lanes x 4 columns
+constexpr int kAfLane = 0, kAfStaged = 1, kAfTiled = 2;
+// the shapes whose matrix a lane keeps in registers (static indices): 0 = any other shape
+// of at most kAfLaneElems elements, walked with run-time bounds
+inline int af_shape_id(int R, int C) {
+  if (R != C) return 0;
+  switch (R) {
+    case 1: return 1;
+    case 3: return 2;
+    case 5: return 3;
+    case 7: return 4;
+    case 8: return 5;
+    default: return 0;
+  }
+}
+struct AfDesc {
+  int64_t so, si, sr, sc;       // element strides of (o, i, r, c)
+  int64_t part_off;             // the tensor's first (Σp², Σu²) partial pair in the workspace
+  int64_t rp_off, cp_off, m_off;  // tiled: row partials [B, R, ncb], column partials [B, nrb, C], m [B]
+  int32_t O, I, R, C;
+  int32_t vec;                  // 1: a vector or a scalar (R = C = 1, slot 2 is `variance`)
+  int32_t regime, shape;        // kAf*; af_shape_id
+  int32_t nparts;               // partial pairs: one per task of the tensor
+  int32_t nrb, ncb;             // tiled: row / column blocks of a matrix
+  float numel;
+  int32_t pad_;
+};
+struct AfTask {
+  int32_t t, b, i, j;  // tensor; lane regimes: b = first matrix; tiled: b = matrix, (i, j) = tile
+  int32_t part, pad_;  // the task's partial pair, relative to the tensor's first
+};
+struct AfTables {  // device pointers (HIP plans)
+  const AfDesc* desc;
+  const AfTask* lane;   // (tensor, block of kBlock matrices)
+  const AfTask* tile;   // (tensor, matrix, tile)
+  const AfTask* fold;   // (tensor, matrix) of the tiled tensors
+  int32_t n_lane, n_tile, n_fold;
+};
+
 }  // namespace gs
 
 // The opaque plan (visible to every TU of the library).
@@ -255,6 +304,12 @@ struct gs_plan {
   int64_t psgd_p = 0, psgd_q = 0;    // elements of the P and Q memory
   void* d_psgd = nullptr;
   gs::PsgdTables psgd_tab{};
+  // Adafactor (gs_adafactor_layout): the descriptors and, on HIP plans, their device copy
+  // with the task tables
+  std::vector<gs::AfDesc> af;
+  int64_t af_total = 0;   // workspace elements (fp32)
+  void* d_af = nullptr;
+  gs::AfTables af_tab{};
   // launch timer ring (gs_plan_timer_enable)
   std::vector<void*> timer_ev;  // [2 * slots]: start, stop
   std::vector<int32_t> timer_kind;  // [slots]: GS_OP_* of the timed launch
@@ -666,6 +721,17 @@ int host_psgd_orthogonalize(gs_plan* p, int which, float* mem, float eps);
 int host_psgd_project(gs_plan* p, int use_error, float* pmem, const float* qmem);
 int host_psgd_backproject(gs_plan* p, const float* pmem, float* qmem);
 int host_psgd_reconstruct(gs_plan* p, const float* pmem, float* qmem, float inv_ws);
+// gs_adafactor_kernels.hip; task tables built by gs_adafactor_layout (gs_plan.cpp)
+struct AfTaskLists {
+  std::vector<AfTask> lane, tile, fold;
+};
+int hip_adafactor_upload(gs_plan* p, const AfTaskLists& l);
+int hip_adafactor_stats(gs_plan* p, const AfHyper& h, float* sums, float* ws, void* stream);
+int hip_adafactor_step(gs_plan* p, const AfHyper& h, float rho, float decay, float eps2, float d, int maximize,
+                       const float* sums, const float* ws, void* stream);
+int host_adafactor_stats(gs_plan* p, const AfHyper& h, float* sums);
+int host_adafactor_step(gs_plan* p, const AfHyper& h, float rho, float decay, float eps2, float d, int maximize,
+                        const float* sums);
 // ---- uint8 quantization (gs_quant_*: gs_quant_kernels.hip / gs_host.cpp) ----
 // A payload's geometry: C channels, Q bytes of quantized values, then the scales and zero points.
 struct QuantLayout {

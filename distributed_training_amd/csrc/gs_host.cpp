@@ -640,6 +640,85 @@ int host_psgd_reconstruct(gs_plan* p, const float* pmem, float* qmem, float inv_
   return GS_OK;
 }
 
+// Adafactor on the host (include/gsync.h, gs_adafactor_*): the device stages restated as plain
+// loops over the descriptor, every sum in ascending index order (a row's sum over c, a column's
+// over r, m over r, Σp² and Σu² over (o, i, r, c)) — the lane regimes' order for the factors,
+// not the tiled regime's nor the device's order for the two per-tensor sums.  Serial: test sizes.
+template <class F>
+static void af_each(gs_plan* p, int t, F f) {
+  const AfDesc& d = p->af[t];
+  const float* G = static_cast<const float*>(slot(p, 1, t));
+  float* P = static_cast<float*>(slot(p, 0, t));
+  float* rv = static_cast<float*>(slot(p, 2, t));
+  float* cv = static_cast<float*>(slot(p, 3, t));
+  for (int64_t o = 0; o < d.O; ++o)
+    for (int64_t i = 0; i < d.I; ++i) {
+      const int64_t b = o * d.I + i, base = o * d.so + i * d.si;
+      f(d, b, G + base, P + base, rv + b * d.R, d.vec ? nullptr : cv + b * d.C);
+    }
+}
+
+int host_adafactor_stats(gs_plan* p, const AfHyper& h, float* sums) {
+  for (int t = 0; t < p->n; ++t) {
+    float sp = 0.f, su = 0.f;
+    af_each(p, t, [&](const AfDesc& d, int64_t, const float* G, float* P, float* rv, float* cv) {
+      if (d.vec) {
+        const float g = G[0];
+        rv[0] = ema_lerp(h.high, h.w, h.wm1, rv[0], g * g);
+        const float u = af_u(g, af_v_vec(h, rv[0]));
+        sp = sp + P[0] * P[0];
+        su = su + u * u;
+        return;
+      }
+      float rsum = 0.f;
+      for (int64_t r = 0; r < d.R; ++r) {
+        float s = 0.f;
+        for (int64_t c = 0; c < d.C; ++c) s = s + G[r * d.sr + c * d.sc] * G[r * d.sr + c * d.sc];
+        rv[r] = af_factor(h, rv[r], s, d.C);
+        rsum = rsum + rv[r];
+      }
+      for (int64_t c = 0; c < d.C; ++c) {
+        float s = 0.f;
+        for (int64_t r = 0; r < d.R; ++r) s = s + G[r * d.sr + c * d.sc] * G[r * d.sr + c * d.sc];
+        cv[c] = af_factor(h, cv[c], s, d.R);
+      }
+      const float m = af_m(h, rsum, d.R);
+      for (int64_t r = 0; r < d.R; ++r)
+        for (int64_t c = 0; c < d.C; ++c) {
+          const int64_t e = r * d.sr + c * d.sc;
+          const float u = af_u(G[e], af_v(h, rv[r], cv[c], m));
+          sp = sp + P[e] * P[e];
+          su = su + u * u;
+        }
+    });
+    sums[2 * t] = sp;
+    sums[2 * t + 1] = su;
+  }
+  return GS_OK;
+}
+
+int host_adafactor_step(gs_plan* p, const AfHyper& h, float rho, float decay, float eps2, float dclip, int maximize,
+                        const float* sums) {
+  for (int t = 0; t < p->n; ++t) {
+    const float scale = af_scale(sums[2 * t], sums[2 * t + 1], p->af[t].numel, eps2, rho, dclip);
+    af_each(p, t, [&](const AfDesc& d, int64_t, const float* G, float* P, float* rv, float* cv) {
+      if (d.vec) {
+        P[0] = af_param(P[0], decay, scale, af_u(G[0], af_v_vec(h, rv[0])), maximize);
+        return;
+      }
+      float rsum = 0.f;
+      for (int64_t r = 0; r < d.R; ++r) rsum = rsum + rv[r];
+      const float m = af_m(h, rsum, d.R);
+      for (int64_t r = 0; r < d.R; ++r)
+        for (int64_t c = 0; c < d.C; ++c) {
+          const int64_t e = r * d.sr + c * d.sc;
+          P[e] = af_param(P[e], decay, scale, af_u(G[e], af_v(h, rv[r], cv[c], m)), maximize);
+        }
+    });
+  }
+  return GS_OK;
+}
+
 // A pairwise sum of terms pushed one by one: a binary counter of finished subtrees, small ones
 // folded first, so at most ceil(log2 n) roundings lie on any path, as in the device's tree
 // (gs_wave.h); its order differs from the device's.

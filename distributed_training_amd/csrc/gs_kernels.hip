@@ -136,6 +136,7 @@ int hip_plan_release(gs_plan* p) {
   if (p->d_lars) (void)hipFree(p->d_lars);  // the LARS scratch, if a gs_lars_* call made one
   if (p->d_muon) (void)hipFree(p->d_muon);  // Muon's tables, if gs_muon_layout made them
   if (p->d_psgd) (void)hipFree(p->d_psgd);  // PowerSGD's tables and scratch, if gs_psgd_layout made them
+  if (p->d_af) (void)hipFree(p->d_af);      // Adafactor's tables, if gs_adafactor_layout made them
   if (p->pinned) (void)hipHostFree(p->pinned);
   return GS_OK;
 }

@@ -255,6 +255,50 @@ GS_HD_INL float muon_poly_out(float b, float c, float acc, float d) { return fma
 GS_HD_INL float muon_apply_out(float a, float acc, float x) { return fmaf(a, x, acc); }
 GS_HD_INL float muon_param(float p, float decay, float adj_lr, float o) { return p * decay - adj_lr * o; }
 
+// ---------------------------------------------------------------- Adafactor
+// Adafactor (gs_adafactor_stats / gs_adafactor_step; include/gsync.h): the factored second
+// moment's element-wise pieces.  Every operation is rounded once; the divisions and the
+// square roots are IEEE (rsqrt is 1 / sqrtf, torch's CPU form).
+struct AfHyper {
+  float w, wm1;  // the lerp weight and ema_form's w - 1
+  bool high;     // ema_form's switch
+  float eps1, eps1sq;
+};
+GS_HD_INL AfHyper af_hyper(double w, double eps1) {
+  AfHyper h;
+  h.w = static_cast<float>(w);
+  ema_form(h.w, &h.wm1, &h.high);
+  h.eps1 = static_cast<float>(eps1);
+  h.eps1sq = static_cast<float>(eps1 * eps1);
+  return h;
+}
+// factor' = lerp(factor, sum / n, w): the sum first, then one true division
+GS_HD_INL float af_factor(const AfHyper& h, float old, float sum, int n) {
+  return ema_lerp(h.high, h.w, h.wm1, old, sum / static_cast<float>(n));
+}
+// m = max(Σ row_var / R, eps1); a NaN stays a NaN, as torch's clamp keeps it
+GS_HD_INL float af_m(const AfHyper& h, float rv_sum, int R) {
+  const float m = rv_sum / static_cast<float>(R);
+  return m < h.eps1 ? h.eps1 : m;
+}
+GS_HD_INL float af_v(const AfHyper& h, float rv, float cv, float m) {
+  const float v = rv * cv / m;
+  return v < h.eps1sq ? h.eps1sq : v;
+}
+GS_HD_INL float af_v_vec(const AfHyper& h, float variance) { return variance < h.eps1sq ? h.eps1sq : variance; }
+// u without its sign (Σu² does not see it; af_param applies it)
+GS_HD_INL float af_u(float g, float v) { return g * (1.0f / sqrtf(v)); }
+// alpha / denom of a tensor from its Σp² (before the decay) and Σu²
+GS_HD_INL float af_scale(float sp, float su, float numel, float eps2, float rho, float d) {
+  const float rms = sqrtf(sp / numel);
+  const float alpha = (rms > eps2 ? rms : eps2) * rho;
+  const float clip = sqrtf(su / numel) / d;
+  return alpha / (clip > 1.f ? clip : 1.f);
+}
+GS_HD_INL float af_param(float p, float decay, float scale, float u, bool maximize) {
+  return maximize ? p * decay + scale * u : p * decay - scale * u;
+}
+
 // ---------------------------------------------------------------- gradient-norm clip
 // Gradient-norm clip folded into an update launch (gs_plan_set_clip): the
 // update's workgroups form the coefficient themselves, so no coefficient

@@ -925,6 +925,124 @@ int gs_psgd_reconstruct(gs_plan* p, const float* pmem, int64_t p_elems, float* q
   return hip_psgd_reconstruct(p, pmem, qmem, static_cast<float>(inv_ws), stream);
 }
 
+// ---- Adafactor: the descriptors, the regimes and the task tables of the grouped launches ----
+int gs_adafactor_layout(gs_plan* p, const int64_t* desc_in, const int32_t* vector, int64_t* layout_out,
+                        int64_t* total_out) {
+  PLAN_OK(p);
+  GS_CHECK_ARG(p->n == 0 || (desc_in != nullptr && vector != nullptr), "gs_adafactor_layout: NULL descriptors");
+  std::vector<AfDesc> desc(p->n);
+  AfTaskLists l;
+  int64_t off = 0;  // floats of the workspace
+  for (int t = 0; t < p->n; ++t) {
+    const int64_t* in = desc_in + 8 * t;
+    const int64_t O = in[0], I = in[1], R = in[2], C = in[3];
+    const std::string who = "gs_adafactor_layout: tensor " + std::to_string(t);
+    if (O <= 0 || I <= 0 || R <= 0 || C <= 0 || p->numel[t] > (int64_t(1) << 30) || O * I * R * C != p->numel[t])
+      return fail(GS_EINVAL, who + " is not an [O, I, R, C] batch of its " + std::to_string(p->numel[t]) + " elements");
+    if (vector[t] && (R != 1 || C != 1)) return fail(GS_EINVAL, who + ": a vector is described with R = C = 1");
+    AfDesc d{};
+    d.O = static_cast<int32_t>(O), d.I = static_cast<int32_t>(I), d.R = static_cast<int32_t>(R), d.C = static_cast<int32_t>(C);
+    // the stride of a dimension of size 1 is never multiplied by anything but 0
+    d.so = O == 1 ? 0 : in[4], d.si = I == 1 ? 0 : in[5], d.sr = R == 1 ? 0 : in[6], d.sc = C == 1 ? 0 : in[7];
+    if (d.so < 0 || d.si < 0 || d.sr < 0 || d.sc < 0) return fail(GS_EINVAL, who + ": negative stride");
+    d.vec = vector[t] != 0;
+    d.numel = static_cast<float>(p->numel[t]);
+    d.shape = af_shape_id(d.R, d.C);
+    const int64_t B = O * I, RC = R * C;
+    d.part_off = off;
+    if (RC <= kAfLaneElems) {
+      const bool contiguous = (C == 1 || d.sc == 1) && (R == 1 || d.sr == C) && (I == 1 || d.si == RC) &&
+                              (O == 1 || d.so == I * RC);
+      d.regime = (contiguous && RC > 1 && d.shape != 0) ? kAfStaged : kAfLane;
+      d.nparts = static_cast<int32_t>((B + kBlock - 1) / kBlock);
+      off += 2 * static_cast<int64_t>(d.nparts);
+      for (int64_t b0 = 0; b0 < B; b0 += kBlock)
+        l.lane.push_back(AfTask{t, static_cast<int32_t>(b0), 0, 0, static_cast<int32_t>(b0 / kBlock), 0});
+    } else {
+      if (C != 1 && d.sc != 1)
+        return fail(GS_EINVAL, who + ": a matrix of more than " + std::to_string(kAfLaneElems) +
+                                   " elements must have unit column stride (got " + std::to_string(d.sc) + ")");
+      d.regime = kAfTiled;
+      d.nrb = static_cast<int32_t>((R + kAfTileRows - 1) / kAfTileRows);
+      d.ncb = static_cast<int32_t>((C + kAfTileCols - 1) / kAfTileCols);
+      const int64_t np = B * d.nrb * d.ncb;
+      if (np > (int64_t(1) << 30)) return fail(GS_EINVAL, who + ": too many tiles");
+      d.nparts = static_cast<int32_t>(np);
+      off += 2 * np;
+      d.rp_off = off, off += B * R * d.ncb;
+      d.cp_off = off, off += B * d.nrb * C;
+      d.m_off = off, off += B;
+      for (int64_t b = 0; b < B; ++b) {
+        l.fold.push_back(AfTask{t, static_cast<int32_t>(b), 0, 0, 0, 0});
+        for (int i = 0; i < d.nrb; ++i)
+          for (int j = 0; j < d.ncb; ++j)
+            l.tile.push_back(AfTask{t, static_cast<int32_t>(b), i, j, static_cast<int32_t>((b * d.nrb + i) * d.ncb + j), 0});
+      }
+    }
+    desc[t] = d;
+    if (layout_out) {
+      layout_out[2 * t] = d.regime;
+      layout_out[2 * t + 1] = d.nparts;
+    }
+  }
+  p->af = desc;
+  p->af_total = off;
+  if (total_out) *total_out = off;
+  if (p->kind != GS_DEV_HIP) return GS_OK;
+  // the lane tasks with the most elements a matrix first (stable: equal shapes keep the list's order)
+  std::stable_sort(l.lane.begin(), l.lane.end(), [&desc](const AfTask& a, const AfTask& b) {
+    return desc[a.t].R * desc[a.t].C > desc[b.t].R * desc[b.t].C;
+  });
+  return hip_adafactor_upload(p, l);
+}
+
+// the layout is made, slots 0..2 of every tensor and slot 3 of every factored one are bound
+static int adafactor_ready(const gs_plan* p, const float* sums, const char* who) {
+  const std::string w(who);
+  if (static_cast<int>(p->af.size()) != p->n) return fail(GS_ESTATE, w + ": call gs_adafactor_layout first");
+  if (p->n != 0 && sums == nullptr) return fail(GS_EINVAL, w + ": NULL sums");
+  if (p->clip_on) return fail(GS_ESTATE, w + ": a gradient-norm clip is set on the plan; clipping is not part of Adafactor");
+  GS_TRY_RET(lars_slots_bound(p, 3, who));
+  for (int t = 0; t < p->n; ++t)
+    if (!p->af[t].vec && p->h_ptrs[static_cast<size_t>(3) * p->n + t] == nullptr)
+      return fail(GS_EINVAL, w + ": slot 3 (col_var) of tensor " + std::to_string(t) + " is not bound");
+  return GS_OK;
+}
+
+int gs_adafactor_stats(gs_plan* p, double w, double eps1, float* sums_out, float* ws, int64_t ws_elems, void* stream) {
+  GsRange range("gs_adafactor_stats");
+  PLAN_OK(p);
+  GS_CHECK_ARG(w >= 0.0 && w <= 1.0, "gs_adafactor_stats: the weight must be in [0, 1]");
+  GS_CHECK_ARG(eps1 >= 0.0, "gs_adafactor_stats: eps1 must be >= 0");
+  GS_TRY_RET(adafactor_ready(p, sums_out, "gs_adafactor_stats"));
+  if (p->n == 0) return GS_OK;
+  if (p->kind == GS_DEV_HOST) return host_adafactor_stats(p, af_hyper(w, eps1), sums_out);
+  GS_CHECK_ARG(ws != nullptr && ws_elems >= p->af_total,
+               "gs_adafactor_stats: workspace of " + std::to_string(ws_elems) + " elements, the layout needs " +
+                   std::to_string(p->af_total));
+  return hip_adafactor_stats(p, af_hyper(w, eps1), sums_out, ws, stream);
+}
+
+int gs_adafactor_step(gs_plan* p, double rho, double lr, double weight_decay, double eps1, double eps2, double d,
+                      int maximize, const float* sums, const float* ws, int64_t ws_elems, void* stream) {
+  GsRange range("gs_adafactor_step");
+  PLAN_OK(p);
+  GS_CHECK_ARG(rho >= 0.0 && eps1 >= 0.0 && eps2 >= 0.0 && d >= 1.0,
+               "gs_adafactor_step: rho, eps1, eps2 must be >= 0 and d >= 1");
+  GS_TRY_RET(adafactor_ready(p, sums, "gs_adafactor_step"));
+  if (p->n == 0) return GS_OK;
+  const float decay = static_cast<float>(1.0 - lr * weight_decay);
+  const AfHyper h = af_hyper(0.0, eps1);
+  if (p->kind == GS_DEV_HOST)
+    return host_adafactor_step(p, h, static_cast<float>(rho), decay, static_cast<float>(eps2), static_cast<float>(d),
+                               maximize != 0, sums);
+  GS_CHECK_ARG(ws != nullptr && ws_elems >= p->af_total,
+               "gs_adafactor_step: workspace of " + std::to_string(ws_elems) + " elements, the layout needs " +
+                   std::to_string(p->af_total));
+  return hip_adafactor_step(p, h, static_cast<float>(rho), decay, static_cast<float>(eps2), static_cast<float>(d),
+                            maximize != 0, sums, ws, stream);
+}
+
 int gs_ema_step(gs_plan* p, int src_dtype, int lowp_dtype, double weight, int copy, void* stream) {
   GsRange range("gs_ema_step");
   PLAN_OK(p);

@@ -473,6 +473,57 @@ class TensorListPlan:
         L.check(L.lib().gs_psgd_reconstruct(self.handle, pp, pn, qp, qn, float(inv_ws), self._stream(stream)),
                 "gs_psgd_reconstruct")
 
+    # ------------------------------------------------------------- Adafactor
+    def adafactor_layout(self, descs: Sequence[Sequence[int]], vectors: Sequence[bool]) -> dict:
+        """Fix the plan's Adafactor regimes (gs_adafactor_layout): tensor t is the batch
+        ``descs[t] = (O, I, R, C, so, si, sr, sc)`` of O x I matrices of R x C elements at
+        those element strides; ``vectors[t]``: a vector or scalar (R = C = 1, slot 2 is its
+        ``variance``).  Returns ``{"total": fp32 elements of the workspace, "tensors":
+        [{"regime", "partials"}]}`` (regime 0 = a lane per matrix, 1 = the same through
+        LDS, 2 = tiled).  Slots: 0 = p, 1 = g, 2 = row_var / variance, 3 = col_var.  Not
+        capturable (it uploads the task tables)."""
+        if len(descs) != self.n or len(vectors) != self.n:
+            raise ValueError(f"plan has {self.n} tensors, got {len(descs)} descriptors, {len(vectors)} flags")
+        flat = [int(x) for dsc in descs for x in dsc]
+        if len(flat) != 8 * self.n:
+            raise ValueError("an Adafactor descriptor is (O, I, R, C, so, si, sr, sc)")
+        out = (ctypes.c_int64 * max(1, 2 * self.n))()
+        total = ctypes.c_int64()
+        L.check(L.lib().gs_adafactor_layout(self.handle, L.i64_array(flat), L.i32_array([int(bool(v)) for v in vectors]),
+                                            out, ctypes.byref(total)), "gs_adafactor_layout")
+        self._adafactor = {"total": int(total.value),
+                           "tensors": [{"regime": int(out[2 * t]), "partials": int(out[2 * t + 1])}
+                                       for t in range(self.n)]}
+        return self._adafactor
+
+    def adafactor_workspace(self) -> torch.Tensor:
+        """An fp32 workspace of the layout's size where the plan runs (no initial contents needed)."""
+        return torch.empty(max(1, self._adafactor["total"]), dtype=torch.float32, device=self.device)
+
+    def _adafactor_ws(self, ws: torch.Tensor):
+        if ws.dtype != torch.float32 or not ws.is_contiguous() or not self._where_plan(ws):
+            raise ValueError("Adafactor workspace: contiguous fp32 where the plan runs")
+        return ws.data_ptr(), ws.numel()
+
+    def adafactor_stats(self, w, eps1, sums: torch.Tensor, ws: torch.Tensor, stream=None):
+        """The factors advance in place (``lerp`` with weight ``w`` towards the row / column
+        means of g²), and ``sums[2t] = Σp²``, ``sums[2t + 1] = Σu²`` of tensor t's update
+        direction, in an order the layout alone fixes (gs_adafactor_stats)."""
+        self._norms_ok(sums)
+        ptr, n = self._adafactor_ws(ws)
+        L.check(L.lib().gs_adafactor_stats(self.handle, float(w), float(eps1), sums.data_ptr(), ptr, n,
+                                           self._stream(stream)), "gs_adafactor_stats")
+
+    def adafactor_step(self, rho, lr, weight_decay, eps1, eps2, d, maximize, sums: torch.Tensor, ws: torch.Tensor,
+                       stream=None):
+        """p = p * (1 - lr*wd) -/+ (alpha / denom) * u, alpha and denom formed on the device
+        from ``sums`` (gs_adafactor_step)."""
+        self._norms_ok(sums)
+        ptr, n = self._adafactor_ws(ws)
+        L.check(L.lib().gs_adafactor_step(self.handle, float(rho), float(lr), float(weight_decay), float(eps1),
+                                          float(eps2), float(d), int(bool(maximize)), sums.data_ptr(), ptr, n,
+                                          self._stream(stream)), "gs_adafactor_step")
+
     # ------------------------------------------------------------------- EMA
     def ema(self, src_dtype, weight=0.0, copy=False, lowp_dtype=None, stream=None):
         """The weight average on slots 0 = average (fp32), 1 = source (``src_dtype``):

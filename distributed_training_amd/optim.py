@@ -21,6 +21,9 @@
   then ``ns_steps`` Newton-Schulz iterations on bf16 MFMA, every stage one grouped
   launch over the whole list of matrices (``3 * ns_steps + 3`` operations per step
   instead of ~20 launches per parameter).
+* :class:`FusedAdafactor` — ``torch.optim.Adafactor`` semantics (T:optim/_adafactor.py):
+  factored second moments, at most 7 grouped launches per step and no host read instead
+  of ~15 launches and two ``.item()`` synchronisations per parameter.
 * :func:`clip_grad_norm_` — ``torch.nn.utils.clip_grad_norm_``
   (T:nn/utils/clip_grad.py:50-186) with a wave-level Σg² reduction and the
   clip coefficient kept on the device (no host sync).
@@ -913,6 +916,145 @@ class FusedMuon(_FusedBase):
                     plan.muon_apply(ws, x, a)
                     x ^= 1
                 plan.muon_update(ws, x, group["lr"], group["weight_decay"], group["adjust_lr_fn"])
+        return loss
+
+
+def _adafactor_descriptor(p: torch.Tensor):
+    """((O, I, R, C, so, si, sr, sc), is a vector) of a parameter FusedAdafactor supports:
+    torch factors the last two dims and batches the ones before them."""
+    what = f"size {tuple(p.size())}, strides {p.stride()}, {p.dtype}"
+    if p.dtype != torch.float32 or p.layout != torch.strided:
+        raise ValueError(f"FusedAdafactor only supports dense fp32 parameters (got {what})")
+    if p.numel() == 0:
+        raise ValueError(f"FusedAdafactor does not support empty parameters (got {what})")
+    if p.ndim == 0:
+        return (1, 1, 1, 1, 0, 0, 0, 0), True
+    if p.ndim == 1 and (p.numel() == 1 or p.stride(0) == 1):
+        return (1, p.numel(), 1, 1, 0, 1, 0, 0), True
+    if p.ndim == 2 and p.is_contiguous():
+        return (1, 1, p.shape[0], p.shape[1], 0, 0, p.shape[1], 1), False
+    if p.ndim == 4 and (p.is_contiguous() or p.is_contiguous(memory_format=torch.channels_last)):
+        if p.shape[2] * p.shape[3] > 64 and p.shape[3] > 1 and p.stride(3) != 1:
+            raise ValueError("FusedAdafactor: a filter of more than 64 taps must be contiguous, not channels_last "
+                             f"(got {what})")
+        return tuple(p.shape) + tuple(p.stride()), False
+    raise ValueError("FusedAdafactor supports 0-D, 1-D, contiguous 2-D and contiguous or channels_last 4-D "
+                     f"parameters (got {what})")
+
+
+class FusedAdafactor(_FusedBase):
+    """Adafactor (``torch.optim.Adafactor``: signature, defaults, validation and the ``step``
+    / ``row_var`` / ``col_var`` / ``variance`` state keys, so ``state_dict()`` moves between
+    the two): a row factor and a column factor in place of a full second moment.
+
+    torch runs about fifteen launches per parameter and step and reads ``param.norm(2)`` and
+    ``update.norm(2)`` back with ``.item()`` — two host synchronisations per parameter, with
+    ``foreach`` too.  Here a step over a (param group, step value) list is at most 7 grouped
+    launches whatever the number of tensors and nothing is read back: ``gs_adafactor_stats``
+    (the factors advance and the per-tensor Σp², Σu² are summed in a fixed order, no
+    atomics) and ``gs_adafactor_step`` (alpha and the update clip formed on the device).
+    The arithmetic is the contract in ``include/gsync.h``: torch's ``_single_tensor_adafactor``
+    in fp32 with the row / column means taken as Σg² / n; the sums' order is the kernels'
+    own, so results agree with torch to fp32 rounding, not bit for bit, and are
+    bit-reproducible run to run.
+
+    Parameters are dense fp32 with fp32 grads in the same layout: 0-D, 1-D, contiguous 2-D,
+    and 4-D filters, contiguous or ``channels_last`` (factored over ``(kh, kw)`` with
+    ``(O, I)`` as the batch, as torch does; a ``channels_last`` filter of more than 64 taps is
+    refused).  Anything else raises ``ValueError``.  A parameter whose grad is None is
+    skipped and its ``step`` does not advance.  ``foreach`` is accepted and ignored.
+
+    Out of scope, each an error: 16-bit parameters or grads, ``grad_scale`` / ``found_inf``
+    (AMP), ``capturable``, ZeRO sharding, the DeepSpeed / ColossalAI shims,
+    ``DDP._register_fused_optim``.
+    """
+
+    _name = "FusedAdafactor"
+    _timer_kinds = (L.GS_OP_ADAFACTOR_STATS, L.GS_OP_ADAFACTOR_STEP)
+
+    def __init__(self, params, lr=1e-2, beta2_decay=-0.8, eps=(None, 1e-3), d=1.0, weight_decay=0.0, *,
+                 foreach=None, maximize=False):
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 <= lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 >= beta2_decay:
+            raise ValueError(f"beta2_decay should be <= 0 but is: {beta2_decay}")
+        if eps[0] is not None and not 0.0 <= eps[0]:
+            raise ValueError(f"epsilon1 should be >= 0 but is: {eps[0]}")
+        if not 0.0 <= eps[1]:
+            raise ValueError(f"epsilon2 should be >= 0 but is: {eps[1]}")
+        if not 1.0 <= d:
+            raise ValueError(f"Clipping threshold d should be >= 1 but is: {d}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight_decay should be >= 0 but is: {weight_decay}")
+        defaults = dict(lr=lr, beta2_decay=beta2_decay, eps=eps, d=d, weight_decay=weight_decay, foreach=foreach,
+                        maximize=maximize)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            for p in group["params"]:
+                _adafactor_descriptor(p)
+
+    def _factors(self, p):
+        """The parameter's state, created as torch creates it; (slot 2, slot 3) of its plan."""
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0, dtype=torch.get_default_dtype())
+            if p.grad.dim() > 1:
+                shape = list(p.grad.shape)
+                st["row_var"] = p.grad.new_zeros(shape[:-1] + [1])
+                st["col_var"] = p.grad.new_zeros(shape[:-2] + [1, shape[-1]])
+            else:
+                st["variance"] = torch.zeros_like(p.grad, memory_format=torch.preserve_format)
+        for key in ("row_var", "col_var", "variance"):  # a loaded state: the kernels index it contiguously
+            if key in st and not (st[key].is_contiguous() and st[key].dtype == torch.float32):
+                st[key] = st[key].to(torch.float32).contiguous()
+        if p.grad.dim() > 1:
+            return st["row_var"], st["col_var"]
+        return st["variance"], None
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self.grad_scale is not None or self.found_inf is not None:
+            raise RuntimeError("FusedAdafactor does not support grad_scale / found_inf (unscale the grads and skip "
+                               "the step on the host)")
+        for group in self.param_groups:
+            eps1, eps2 = group["eps"]
+            if eps1 is None:
+                eps1 = torch.finfo(torch.float32).eps
+            lr = group["lr"].item() if isinstance(group["lr"], torch.Tensor) else group["lr"]
+            cohorts: dict = {}  # step value -> (params, grads, slot 2, slot 3): w and rho are launch scalars
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                self._check_param(p)
+                if p.grad.dtype != torch.float32:
+                    raise RuntimeError(f"FusedAdafactor expects fp32 grads (got {p.grad.dtype})")
+                s2, s3 = self._factors(p)
+                st = self.state[p]
+                st["step"] += 1
+                lists = cohorts.setdefault(st["step"].item(), ([], [], [], []))  # a CPU scalar: no device read
+                for lst, x in zip(lists, (p, p.grad, s2, s3)):
+                    lst.append(x)
+            for step, (ps, gs, s2, s3) in cohorts.items():
+                plan = self._plans.get(ps)
+                plan.set_ptrs(0, ps)
+                plan.set_ptrs(1, gs)
+                for slot, lst in ((2, s2), (3, s3)):  # the factors are smaller than their tensor: raw pointers
+                    plan.set_ptrs(slot, [None if x is None else x.data_ptr() for x in lst])
+                ws = getattr(plan, "_adafactor_space", None)
+                if ws is None:
+                    descs, vectors = zip(*(_adafactor_descriptor(p) for p in ps))
+                    plan.adafactor_layout(descs, vectors)
+                    ws = plan._adafactor_space = plan.adafactor_workspace()
+                    plan._norms = torch.zeros(2 * len(ps), dtype=torch.float32, device=ps[0].device)
+                plan.adafactor_stats(step ** group["beta2_decay"], eps1, plan._norms, ws)
+                plan.adafactor_step(min(lr, 1 / (step ** 0.5)), lr, group["weight_decay"], eps1, eps2, group["d"],
+                                    group["maximize"], plan._norms, ws)
         return loss
 
 

@@ -219,6 +219,8 @@ int64_t gs_plan_task_units(gs_plan* p);
 #define GS_OP_PSGD_PROJECT 20
 #define GS_OP_PSGD_BACKPROJECT 21 /* gs_psgd_backproject: the partial pass and its fold, one record each */
 #define GS_OP_PSGD_RECONSTRUCT 22
+#define GS_OP_ADAFACTOR_STATS 23 /* gs_adafactor_stats: one record per launch (up to 5) */
+#define GS_OP_ADAFACTOR_STEP 24  /* gs_adafactor_step: one record per launch (up to 2) */
 int gs_plan_timer_enable(gs_plan* p, int n_slots);
 int gs_plan_timer_read(gs_plan* p, float* ms_out, int32_t* kind_out, int cap);
 /* register the per-tensor pointers of one slot (uploads on change, ordered on `stream`) */
@@ -629,6 +631,63 @@ int gs_psgd_project(gs_plan* p, int use_error, float* pmem, int64_t p_elems, con
 int gs_psgd_backproject(gs_plan* p, const float* pmem, int64_t p_elems, float* qmem, int64_t q_elems, void* stream);
 int gs_psgd_reconstruct(gs_plan* p, const float* pmem, int64_t p_elems, float* qmem, int64_t q_elems, double inv_ws,
                         void* stream);
+
+/* Adafactor (Shazeer & Stern 2018; torch.optim.Adafactor): a row factor and a column factor
+ * in place of a full second moment.  One plan holds a ragged list of tensors; a step is at
+ * most 7 launches whatever their number: gs_adafactor_stats (up to 5), gs_adafactor_step
+ * (up to 2), and no value is read back by the host.
+ *
+ * Tensor t is the descriptor desc[8t..8t+7] = (O, I, R, C, so, si, sr, sc): a batch of O x I
+ * matrices of R x C elements, element (o, i, r, c) at o*so + i*si + r*sr + c*sc (a 2-D weight:
+ * O = I = 1; a filter [O, I, kh, kw] is factored over (kh, kw), contiguous or channels_last).
+ * vector[t] != 0: a vector or a scalar, R = C = 1, which keeps a full `variance`.
+ * Slots: 0 = p, 1 = g (same strides), 2 = row_var [O, I, R] or variance [O * I], 3 = col_var
+ * [O, I, C] (unbound for a vector); slots 2 and 3 contiguous; all fp32.
+ * Arithmetic (torch's _single_tensor_adafactor in fp32; every operation rounded once, no fma).
+ * Formed on the host in double and rounded to fp32: w (= step ** beta2_decay), eps1,
+ * eps1*eps1, rho (= min(lr, 1/sqrt(step))), 1 - lr*wd, eps2, d.
+ *   gs_adafactor_stats, per matrix of the batch:
+ *     row_var_i = lerp(row_var_i, (Σ_j g_ij²) / C, w)    the sum, then ONE true division;
+ *     col_var_j = lerp(col_var_j, (Σ_i g_ij²) / R, w)    lerp in gs_ema_step's form
+ *     m    = max((Σ_i row_var_i) / R, eps1)
+ *     v_ij = max(row_var_i * col_var_j / m, eps1²)       product, then the division
+ *   a vector:  variance = lerp(variance, g*g, w);  v = max(variance, eps1²)
+ *     u    = g * (1 / sqrt(v))                           IEEE sqrt and division (torch's CPU rsqrt)
+ *     sums_out[2t] = Σp² (before the decay), sums_out[2t + 1] = Σu²
+ *   gs_adafactor_step, per tensor, on the device from sums:
+ *     alpha = max(eps2, sqrt(Σp² / numel)) * rho;  denom = max(1, sqrt(Σu² / numel) / d)
+ *     p = p * (1 - lr*wd) -/+ (alpha / denom) * u        u recomputed from g and the new factors
+ *                                                        (+ with maximize)
+ * Orders of accumulation, fixed by the layout alone (no atomics: bit-reproducible run to run):
+ *   matrices of R*C <= 64 elements (and vectors): one lane owns a matrix; a row's sum runs over
+ *     ascending j, a column's over ascending i, m over ascending i; the lane's Σp², Σu² over
+ *     ascending (i, j); then the wave tree of the 64 lanes and the 4 waves in order give the
+ *     partial of a block of 256 matrices (a contiguous batch of 3x3, 5x5, 7x7 or 8x8 matrices
+ *     sums Σp² by the block's coalesced sweep instead: a thread's elements k, k + 1024, ...);
+ *   larger matrices (unit column stride), in 64 x 256 tiles: a row's partial of a tile is a
+ *     lane's 4 columns in order, then the wave tree; a column's partial adds a wave's 16 rows in
+ *     order, then the 4 waves in order; tiles are added in ascending block order; m adds rows
+ *     k, k + 256, .. per thread, then the wave tree and the 4 waves; a tile's Σp², Σu² add a
+ *     lane's elements row by row, then the wave tree and the 4 waves;
+ *   a tensor's partials: thread k adds k, k + 256, .. in order, then the wave tree, the 4 waves.
+ * The host backend adds everything in ascending index order, so (as for Muon and PowerSGD)
+ * host and device agree up to the accumulation order only.
+ *
+ * gs_adafactor_layout fixes the regimes: layout_out[2t] = 0 (lane per matrix), 1 (the same
+ * through LDS) or 2 (tiled), layout_out[2t + 1] = the tensor's partial pairs; *total_out = the
+ * fp32 elements of the caller's workspace (no initial contents needed; gs_adafactor_step reads
+ * what gs_adafactor_stats left in it).  GS_EINVAL: a descriptor that does not cover numel, a
+ * vector with R*C != 1, a matrix of more than 64 elements with sc != 1.  On a HIP plan it
+ * uploads the task tables (synchronous: not capturable).  The host backend ignores ws.
+ * Not part of Adafactor here: grad_scale / found_inf, a plan clip (GS_ESTATE), a hyper source.
+ * replaces: T:optim/_adafactor.py _single_tensor_adafactor / _multi_tensor_adafactor (per
+ *           parameter ~15 launches and the two .item() reads of param.norm(2), update.norm(2)) */
+int gs_adafactor_layout(gs_plan* p, const int64_t* desc, const int32_t* vector, int64_t* layout_out,
+                        int64_t* total_out);
+int gs_adafactor_stats(gs_plan* p, double w, double eps1, float* sums_out, float* ws, int64_t ws_elems, void* stream);
+/* sums: gs_adafactor_stats' output for this step; eps1 must be the same in both calls */
+int gs_adafactor_step(gs_plan* p, double rho, double lr, double weight_decay, double eps1, double eps2, double d,
+                      int maximize, const float* sums, const float* ws, int64_t ws_elems, void* stream);
 
 /* EMA / SWA weight averaging: one pass a' = lerp(a, s, w) over a whole model.
  * Slots: 0 = the average a (f32), 1 = the source s (src_dtype: f32, bf16 or f16, converted
