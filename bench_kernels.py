@@ -511,6 +511,8 @@ def main():
         muon_row(args, dev, shapes)
     if want("adafactor"):
         adafactor_row(args, dev, shapes)
+    if want("came"):
+        came_row(args, dev, shapes)
     if want("psgd"):
         for rank in (1, 4):
             psgd_row(args, dev, rank)
@@ -611,6 +613,53 @@ def adafactor_row(args, dev, shapes, repeats=5):
            "fused_ms": med(t_f), "torch_ms": med(t_t), "fused_ms_repeats": t_f, "torch_ms_repeats": t_t,
            "fused_launches": launches, "torch_launches": sum(15 if p.ndim > 1 else 9 for p in mine),
            "torch_host_reads": 2 * len(mine), "alg_bytes": nbytes, "fused_GBps": gbs,
+           "fused_frac_of_8TBps": gbs / HBM_PEAK, "speedup": med(t_t) / med(t_f)}
+    print(json.dumps(row), flush=True)
+
+
+def came_row(args, dev, shapes, repeats=5):
+    """FusedCAME against the plain per-parameter torch restatement of the same arithmetic
+    (tests/_came_common.py: came_reference) on the model's parameter list (filters
+    channels_last), measured as adafactor_row measures.  Traffic model: 24 B per element a
+    lane owns (g read by the stats pass; g, m, p read and m, p written by the fused launch),
+    32 B per element of a tiled matrix (g read by the sums and by the Σu² pass; g, m read and
+    m written by the moment pass; m, p read and p written by the update)."""
+    from distributed_training_amd.optim import FusedCAME
+    from tests._came_common import came_reference
+
+    g = torch.Generator(device=dev).manual_seed(1)
+
+    def make(s):
+        x = torch.randn(tuple(s), device=dev, generator=g)
+        return x.contiguous(memory_format=torch.channels_last) if len(s) == 4 else x
+
+    mine = [torch.nn.Parameter(make(s)) for s in shapes]
+    theirs = [torch.nn.Parameter(p.detach().clone()) for p in mine]
+    for p, q in zip(mine, theirs):
+        p.grad = make(p.shape) * 0.01
+        q.grad = p.grad.clone()
+    fused, state = FusedCAME(mine, lr=1e-6), {}
+    nbytes = sum(p.numel() * (32 if p.ndim > 1 and p.shape[-1] * p.shape[-2] > 64 else 24) for p in mine)
+
+    def run(step):
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        return timeit_batched(step, args.iters)
+
+    t_f, t_t = [], []
+    for _ in range(repeats):
+        t_f.append(run(fused.step))
+        t_t.append(run(lambda: came_reference(theirs, state, lr=1e-6)))
+    fused.enable_kernel_timer()
+    fused.step()
+    torch.cuda.synchronize()
+    launches = len(fused.kernel_ms())
+    med = lambda ts: sorted(ts)[len(ts) // 2]  # noqa: E731
+    gbs = nbytes / (med(t_f) * 1e-3) / 1e9
+    row = {"kernel": "came_step", "model": args.model, "tensors": len(mine), "tag": args.tag,
+           "fused_ms": med(t_f), "torch_ms": med(t_t), "fused_ms_repeats": t_f, "torch_ms_repeats": t_t,
+           "fused_launches": launches, "alg_bytes": nbytes, "fused_GBps": gbs,
            "fused_frac_of_8TBps": gbs / HBM_PEAK, "speedup": med(t_t) / med(t_f)}
     print(json.dumps(row), flush=True)
 

@@ -3,7 +3,7 @@ engine (libgsync) behind the reference's DDP / DeepSpeed / ColossalAI wrappers.
 
 Public surface:
   DistributedDataParallel   drop-in for torch.nn.parallel.DistributedDataParallel
-  FusedSGD / FusedAdam / FusedAdamW / FusedLARS / FusedLAMB / FusedMuon / FusedAdafactor / clip_grad_norm_
+  FusedSGD / FusedAdam / FusedAdamW / FusedLARS / FusedLAMB / FusedMuon / FusedAdafactor / FusedCAME / clip_grad_norm_
   Communicator              libgsync-owned RCCL communicator
   PowerSGDState / powerSGD_hook  torch's PowerSGD gradient-compression comm hook on grouped HIP kernels
   quantization_pertensor_hook / quantization_perchannel_hook  torch's uint8 gradient-quantization comm
@@ -34,6 +34,6 @@ from .evaluation import Metrics, evaluate  # noqa: F401
 from .loss import CrossEntropyLoss, cross_entropy  # noqa: F401
 from .flatten import copy_flat_to, flatten_dense_tensors, unflatten_dense_tensors  # noqa: F401
 from .multi_tensor import TensorListPlan  # noqa: F401
-from .optim import FusedAdafactor, FusedAdam, FusedAdamW, FusedLAMB, FusedLARS, FusedMuon, FusedSGD, clip_grad_norm_  # noqa: F401
+from .optim import FusedAdafactor, FusedAdam, FusedAdamW, FusedCAME, FusedLAMB, FusedLARS, FusedMuon, FusedSGD, clip_grad_norm_  # noqa: F401
 
 __version__ = "0.1.0"

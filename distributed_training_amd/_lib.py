@@ -30,7 +30,7 @@ GS_F32, GS_BF16, GS_F16, GS_F64, GS_I64, GS_I32, GS_U8 = 0, 1, 2, 3, 4, 5, 6
 GS_DEV_HOST, GS_DEV_HIP = 0, 1
 GS_SUM, GS_PROD, GS_MAX, GS_MIN, GS_AVG = 0, 1, 2, 3, 4
 GS_SCALE_NONE, GS_SCALE_MUL, GS_SCALE_DIV = 0, 1, 2
-GS_PLAN_SLOTS = 5
+GS_PLAN_SLOTS = 7
 GS_RED_GROUPS = 64  # the fused reduction's group sums (one per lane of the folding wave)
 GS_RED_PARTIALS = 1024  # gs_sqnorm_partial_out: the caller's buffer, at most this many partial sums
 GS_BKT_AUTO_COLLECTIVE = 1
@@ -46,6 +46,7 @@ GS_OP_EMA = 13
 GS_OP_MUON_PREP, GS_OP_MUON_GRAM, GS_OP_MUON_POLY, GS_OP_MUON_APPLY, GS_OP_MUON_UPDATE = 14, 15, 16, 17, 18
 GS_OP_PSGD_ORTH, GS_OP_PSGD_PROJECT, GS_OP_PSGD_BACKPROJECT, GS_OP_PSGD_RECONSTRUCT = 19, 20, 21, 22
 GS_OP_ADAFACTOR_STATS, GS_OP_ADAFACTOR_STEP = 23, 24
+GS_OP_CAME_STATS, GS_OP_CAME_MOMENT, GS_OP_CAME_STEP = 25, 26, 27
 GS_EMA_EMA, GS_EMA_SWA, GS_EMA_WARMUP = 0, 1, 2
 GS_QUANT_PARTIALS = 1024  # gs_quant_pertensor: the (lo, hi) pairs of its scratch
 
@@ -179,6 +180,9 @@ SIGNATURES = {
     "gs_adafactor_layout": (_c_int, [_vp, _vp, _vp, _vp, _vp]),
     "gs_adafactor_stats": (_c_int, [_vp, _c_d, _c_d, _vp, _vp, _c_i64, _vp]),
     "gs_adafactor_step": (_c_int, [_vp, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _c_int, _vp, _vp, _c_i64, _vp]),
+    "gs_came_stats": (_c_int, [_vp, _c_d, _c_d, _vp, _vp, _c_i64, _vp]),
+    "gs_came_moment": (_c_int, [_vp, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _c_i64, _vp]),
+    "gs_came_step": (_c_int, [_vp, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d, _vp, _vp, _c_i64, _vp]),
     "gs_quant_payload_bytes": (_c_i64, [_c_i64, _c_int]),
     "gs_quant_perchannel": (_c_int, [_c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _vp]),
     "gs_quant_pertensor": (_c_int, [_c_int, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),

@@ -732,6 +732,13 @@ int hip_adafactor_step(gs_plan* p, const AfHyper& h, float rho, float decay, flo
 int host_adafactor_stats(gs_plan* p, const AfHyper& h, float* sums);
 int host_adafactor_step(gs_plan* p, const AfHyper& h, float rho, float decay, float eps2, float d, int maximize,
                         const float* sums);
+// gs_came_kernels.hip: CAME on gs_adafactor_layout's descriptors and task tables
+int hip_came_stats(gs_plan* p, const CameHyper& h, float* sums, float* ws, void* stream);
+int hip_came_moment(gs_plan* p, const CameHyper& h, const float* sums, float* ws, void* stream);
+int hip_came_step(gs_plan* p, const CameHyper& h, const float* sums, const float* ws, void* stream);
+int host_came_stats(gs_plan* p, const CameHyper& h, float* sums);
+int host_came_moment(gs_plan* p, const CameHyper& h, const float* sums);
+int host_came_step(gs_plan* p, const CameHyper& h);
 // ---- uint8 quantization (gs_quant_*: gs_quant_kernels.hip / gs_host.cpp) ----
 // A payload's geometry: C channels, Q bytes of quantized values, then the scales and zero points.
 struct QuantLayout {

@@ -352,8 +352,9 @@ __device__ __forceinline__ float block_reduce(float v) {
 // Everything a lane-access needs about its tensor (load_tv): read once per group of
 // full chunks through scalar loads, or, for a mixed chunk, staged once per chunk in LDS
 // (one entry per tensor of the span, chunk_mixed_lds).
+constexpr int kEngineSlots = 5;  // the rows a streaming op addresses (rows 5, 6: CAME's grouped kernels only)
 struct TV {
-  void* ptr[GS_PLAN_SLOTS];
+  void* ptr[kEngineSlots];
   int64_t numel;
   int64_t off;
   uint32_t align;
@@ -416,7 +417,7 @@ __device__ __forceinline__ TV load_tv(const Op& op, const PlanArgs& P, int t) {
   const uint32_t a = SCALAR ? cload(P.align, t) : P.align[t];
   uint32_t bits = 0;
 #pragma unroll
-  for (int s = 0; s < GS_PLAN_SLOTS; ++s) {
+  for (int s = 0; s < kEngineSlots; ++s) {
     const int64_t r = static_cast<int64_t>(op.phys(s)) * P.n + t;
     v.ptr[s] = SCALAR ? cload(P.ptrs, r) : P.ptrs[r];
     bits |= ((a >> op.phys(s)) & 1u) << s;

@@ -719,6 +719,115 @@ int host_adafactor_step(gs_plan* p, const AfHyper& h, float rho, float decay, fl
   return GS_OK;
 }
 
+// CAME on the host (include/gsync.h, gs_came_*): the three stages as plain loops over the
+// descriptor, every sum in ascending index order, as host_adafactor_* above.  gs_came_moment
+// advances m, R and C of every tensor here (on the device the lane regimes do that inside
+// gs_came_step); gs_came_step then only writes p.  Serial: test sizes.
+struct CameMat {
+  const float* G;
+  float *P, *M, *rv, *cv, *Rv, *Cv;
+};
+template <class F>
+static void came_each(gs_plan* p, int t, F f) {
+  const AfDesc& d = p->af[t];
+  const float* G = static_cast<const float*>(slot(p, 1, t));
+  float* P = static_cast<float*>(slot(p, 0, t));
+  float* M = static_cast<float*>(slot(p, 4, t));
+  float* s[4] = {static_cast<float*>(slot(p, 2, t)), static_cast<float*>(slot(p, 3, t)),
+                 static_cast<float*>(slot(p, 5, t)), static_cast<float*>(slot(p, 6, t))};
+  for (int64_t o = 0; o < d.O; ++o)
+    for (int64_t i = 0; i < d.I; ++i) {
+      const int64_t b = o * d.I + i, base = o * d.so + i * d.si;
+      if (d.vec)
+        f(d, CameMat{G + base, P + base, M + base, s[0] + b, nullptr, nullptr, nullptr});
+      else
+        f(d, CameMat{G + base, P + base, M + base, s[0] + b * d.R, s[1] + b * d.C, s[2] + b * d.R, s[3] + b * d.C});
+    }
+}
+static float came_row_mean(const AfDesc& d, const float* rv) {
+  float s = 0.f;
+  for (int64_t r = 0; r < d.R; ++r) s = s + rv[r];
+  return came_mean(s, d.R);
+}
+
+int host_came_stats(gs_plan* p, const CameHyper& h, float* sums) {
+  for (int t = 0; t < p->n; ++t) {
+    float su = 0.f;
+    came_each(p, t, [&](const AfDesc& d, const CameMat& x) {
+      if (d.vec) {
+        x.rv[0] = came_ema(x.rv[0], came_sq(x.G[0], h.eps1), h.b2, h.omb2);
+        const float u = x.G[0] * came_cf(x.rv[0]);
+        su = su + u * u;
+        return;
+      }
+      for (int64_t r = 0; r < d.R; ++r) {
+        float s = 0.f;
+        for (int64_t c = 0; c < d.C; ++c) s = s + came_sq(x.G[r * d.sr + c * d.sc], h.eps1);
+        x.rv[r] = came_factor(x.rv[r], s, d.C, h.b2, h.omb2);
+      }
+      for (int64_t c = 0; c < d.C; ++c) {
+        float s = 0.f;
+        for (int64_t r = 0; r < d.R; ++r) s = s + came_sq(x.G[r * d.sr + c * d.sc], h.eps1);
+        x.cv[c] = came_factor(x.cv[c], s, d.R, h.b2, h.omb2);
+      }
+      const float mean = came_row_mean(d, x.rv);
+      for (int64_t r = 0; r < d.R; ++r)
+        for (int64_t c = 0; c < d.C; ++c) {
+          const float u = came_dir(x.G[r * d.sr + c * d.sc], came_rf(x.rv[r], mean), came_cf(x.cv[c]));
+          su = su + u * u;
+        }
+    });
+    sums[t] = su;
+  }
+  return GS_OK;
+}
+
+int host_came_moment(gs_plan* p, const CameHyper& h, const float* sums) {
+  std::vector<float> qc;
+  for (int t = 0; t < p->n; ++t) {
+    const float denom = came_denom(sums[t], p->af[t].numel, h.d);
+    came_each(p, t, [&](const AfDesc& d, const CameMat& x) {
+      if (d.vec) {
+        x.M[0] = came_ema(x.M[0], x.G[0] * came_cf(x.rv[0]) / denom, h.b1, h.omb1);
+        return;
+      }
+      const float mean = came_row_mean(d, x.rv);
+      qc.assign(d.C, 0.f);
+      for (int64_t r = 0; r < d.R; ++r) {
+        float s = 0.f;
+        for (int64_t c = 0; c < d.C; ++c) {
+          const int64_t e = r * d.sr + c * d.sc;
+          const float uh = came_dir(x.G[e], came_rf(x.rv[r], mean), came_cf(x.cv[c])) / denom;
+          x.M[e] = came_ema(x.M[e], uh, h.b1, h.omb1);
+          const float q = came_res(uh, x.M[e], h.eps2);
+          s = s + q;
+          qc[c] = qc[c] + q;
+        }
+        x.Rv[r] = came_factor(x.Rv[r], s, d.C, h.b3, h.omb3);
+      }
+      for (int64_t c = 0; c < d.C; ++c) x.Cv[c] = came_factor(x.Cv[c], qc[c], d.R, h.b3, h.omb3);
+    });
+  }
+  return GS_OK;
+}
+
+int host_came_step(gs_plan* p, const CameHyper& h) {
+  for (int t = 0; t < p->n; ++t)
+    came_each(p, t, [&](const AfDesc& d, const CameMat& x) {
+      if (d.vec) {
+        x.P[0] = came_param(h, x.P[0], x.M[0]);
+        return;
+      }
+      const float Mean = came_row_mean(d, x.Rv);
+      for (int64_t r = 0; r < d.R; ++r)
+        for (int64_t c = 0; c < d.C; ++c) {
+          const int64_t e = r * d.sr + c * d.sc;
+          x.P[e] = came_param(h, x.P[e], came_dir(x.M[e], came_rf(x.Rv[r], Mean), came_cf(x.Cv[c])));
+        }
+    });
+  return GS_OK;
+}
+
 // A pairwise sum of terms pushed one by one: a binary counter of finished subtrees, small ones
 // folded first, so at most ceil(log2 n) roundings lie on any path, as in the device's tree
 // (gs_wave.h); its order differs from the device's.

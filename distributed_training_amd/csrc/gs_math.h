@@ -299,6 +299,50 @@ GS_HD_INL float af_param(float p, float decay, float scale, float u, bool maximi
   return maximize ? p * decay + scale * u : p * decay - scale * u;
 }
 
+// ---------------------------------------------------------------- CAME
+// CAME (gs_came_stats / gs_came_moment / gs_came_step; include/gsync.h): the element-wise
+// pieces.  Every operation is rounded once; divisions and square roots are IEEE.
+struct CameHyper {
+  float b1, omb1, b2, omb2, b3, omb3;  // the betas and 1 - beta (formed in double)
+  float eps1, eps2, d;
+  float lr, wdlr;  // lr, -weight_decay * lr (formed in double)
+  bool decay;      // weight_decay != 0
+};
+GS_HD_INL CameHyper came_hyper(double b1, double b2, double b3, double eps1, double eps2, double d, double lr,
+                               double wd) {
+  CameHyper h;
+  h.b1 = static_cast<float>(b1), h.omb1 = static_cast<float>(1.0 - b1);
+  h.b2 = static_cast<float>(b2), h.omb2 = static_cast<float>(1.0 - b2);
+  h.b3 = static_cast<float>(b3), h.omb3 = static_cast<float>(1.0 - b3);
+  h.eps1 = static_cast<float>(eps1), h.eps2 = static_cast<float>(eps2), h.d = static_cast<float>(d);
+  h.lr = static_cast<float>(lr), h.wdlr = static_cast<float>(-wd * lr);
+  h.decay = wd != 0.0;
+  return h;
+}
+GS_HD_INL float came_ema(float old, float x, float b, float omb) { return old * b + x * omb; }
+GS_HD_INL float came_sq(float g, float eps1) { return g * g + eps1; }
+GS_HD_INL float came_mean(float sum, int n) { return sum / static_cast<float>(n); }
+// factor' = factor*b + (sum / n)*(1 - b): the sum first, then one true division
+GS_HD_INL float came_factor(float old, float sum, int n, float b, float omb) {
+  return came_ema(old, came_mean(sum, n), b, omb);
+}
+GS_HD_INL float came_rf(float r, float mean) { return 1.0f / sqrtf(r / mean); }  // a row's factor
+GS_HD_INL float came_cf(float c) { return 1.0f / sqrtf(c); }                     // a column's (or a vector's v)
+GS_HD_INL float came_dir(float x, float rf, float cf) { return x * (rf * cf); }  // u from g, upd from m
+// max(1, sqrt(Σu² / numel) / d); a NaN stays a NaN, as clamp_ keeps it
+GS_HD_INL float came_denom(float su, float numel, float d) {
+  const float x = sqrtf(su / numel) / d;
+  return x < 1.f ? 1.f : x;
+}
+GS_HD_INL float came_res(float uh, float m, float eps2) {
+  const float e = uh - m;
+  return e * e + eps2;
+}
+GS_HD_INL float came_param(const CameHyper& h, float p, float upd) {
+  if (h.decay) p = p + p * h.wdlr;
+  return p - h.lr * upd;
+}
+
 // ---------------------------------------------------------------- gradient-norm clip
 // Gradient-norm clip folded into an update launch (gs_plan_set_clip): the
 // update's workgroups form the coefficient themselves, so no coefficient

@@ -1043,6 +1043,62 @@ int gs_adafactor_step(gs_plan* p, double rho, double lr, double weight_decay, do
                             maximize != 0, sums, ws, stream);
 }
 
+// ---- CAME: three stages on Adafactor's layout ----
+// the layout is made; slots 0..2 and 4 of every tensor, 3, 5 and 6 of every factored one are bound
+static int came_ready(const gs_plan* p, const float* sums, const float* ws, int64_t ws_elems, const char* who) {
+  const std::string w(who);
+  if (static_cast<int>(p->af.size()) != p->n) return fail(GS_ESTATE, w + ": call gs_adafactor_layout first");
+  if (p->n != 0 && sums == nullptr) return fail(GS_EINVAL, w + ": NULL sums");
+  if (p->clip_on) return fail(GS_ESTATE, w + ": a gradient-norm clip is set on the plan; clipping is not part of CAME");
+  GS_TRY_RET(lars_slots_bound(p, 3, who));
+  for (int t = 0; t < p->n; ++t)
+    for (int s = 3; s < 7; ++s)
+      if ((s == 4 || !p->af[t].vec) && p->h_ptrs[static_cast<size_t>(s) * p->n + t] == nullptr)
+        return fail(GS_EINVAL, w + ": slot " + std::to_string(s) + " of tensor " + std::to_string(t) + " is not bound");
+  if (p->kind != GS_DEV_HOST && p->n != 0 && (ws == nullptr || ws_elems < p->af_total))
+    return fail(GS_EINVAL, w + ": workspace of " + std::to_string(ws_elems) + " elements, the layout needs " +
+                               std::to_string(p->af_total));
+  return GS_OK;
+}
+static bool came_hyper_ok(double b1, double b3, double eps2, double d) {
+  return b1 >= 0.0 && b1 <= 1.0 && b3 >= 0.0 && b3 <= 1.0 && eps2 >= 0.0 && d > 0.0;
+}
+
+int gs_came_stats(gs_plan* p, double beta2, double eps1, float* sums_out, float* ws, int64_t ws_elems, void* stream) {
+  GsRange range("gs_came_stats");
+  PLAN_OK(p);
+  GS_CHECK_ARG(beta2 >= 0.0 && beta2 <= 1.0 && eps1 >= 0.0, "gs_came_stats: beta2 must be in [0, 1], eps1 >= 0");
+  GS_TRY_RET(came_ready(p, sums_out, ws, ws_elems, "gs_came_stats"));
+  if (p->n == 0) return GS_OK;
+  const CameHyper h = came_hyper(0.0, beta2, 0.0, eps1, 0.0, 1.0, 0.0, 0.0);
+  if (p->kind == GS_DEV_HOST) return host_came_stats(p, h, sums_out);
+  return hip_came_stats(p, h, sums_out, ws, stream);
+}
+
+int gs_came_moment(gs_plan* p, double beta1, double beta3, double eps2, double d, const float* sums, float* ws,
+                   int64_t ws_elems, void* stream) {
+  GsRange range("gs_came_moment");
+  PLAN_OK(p);
+  GS_CHECK_ARG(came_hyper_ok(beta1, beta3, eps2, d), "gs_came_moment: betas must be in [0, 1], eps2 >= 0, d > 0");
+  GS_TRY_RET(came_ready(p, sums, ws, ws_elems, "gs_came_moment"));
+  if (p->n == 0) return GS_OK;
+  const CameHyper h = came_hyper(beta1, 0.0, beta3, 0.0, eps2, d, 0.0, 0.0);
+  if (p->kind == GS_DEV_HOST) return host_came_moment(p, h, sums);
+  return hip_came_moment(p, h, sums, ws, stream);
+}
+
+int gs_came_step(gs_plan* p, double beta1, double beta3, double eps2, double d, double lr, double weight_decay,
+                 const float* sums, const float* ws, int64_t ws_elems, void* stream) {
+  GsRange range("gs_came_step");
+  PLAN_OK(p);
+  GS_CHECK_ARG(came_hyper_ok(beta1, beta3, eps2, d), "gs_came_step: betas must be in [0, 1], eps2 >= 0, d > 0");
+  GS_TRY_RET(came_ready(p, sums, ws, ws_elems, "gs_came_step"));
+  if (p->n == 0) return GS_OK;
+  const CameHyper h = came_hyper(beta1, 0.0, beta3, 0.0, eps2, d, lr, weight_decay);
+  if (p->kind == GS_DEV_HOST) return host_came_step(p, h);
+  return hip_came_step(p, h, sums, ws, stream);
+}
+
 int gs_ema_step(gs_plan* p, int src_dtype, int lowp_dtype, double weight, int copy, void* stream) {
   GsRange range("gs_ema_step");
   PLAN_OK(p);

@@ -524,6 +524,38 @@ class TensorListPlan:
                                           float(eps2), float(d), int(bool(maximize)), sums.data_ptr(), ptr, n,
                                           self._stream(stream)), "gs_adafactor_step")
 
+    # ------------------------------------------------------------------ CAME
+    def _came_sums(self, sums: torch.Tensor):
+        if sums.dtype != torch.float32 or not sums.is_contiguous() or sums.numel() < self.n or \
+                not self._where_plan(sums):
+            raise ValueError(f"CAME sums: contiguous fp32[>= {self.n}] where the plan runs")
+
+    def came_stats(self, beta2, eps1, sums: torch.Tensor, ws: torch.Tensor, stream=None):
+        """Stage 1 of CAME on :meth:`adafactor_layout`'s descriptors and workspace: r and c
+        (slots 2, 3) advance towards the row / column means of g² + eps1 and ``sums[t]`` =
+        Σu² of tensor t, in an order the layout alone fixes (gs_came_stats)."""
+        self._came_sums(sums)
+        ptr, n = self._adafactor_ws(ws)
+        L.check(L.lib().gs_came_stats(self.handle, float(beta2), float(eps1), sums.data_ptr(), ptr, n,
+                                      self._stream(stream)), "gs_came_stats")
+
+    def came_moment(self, beta1, beta3, eps2, d, sums: torch.Tensor, ws: torch.Tensor, stream=None):
+        """Stage 2 of the tiled tensors: m (slot 4) advances towards the clipped direction and
+        R, C (slots 5, 6) towards the row / column means of (û - m)² + eps2 (gs_came_moment)."""
+        self._came_sums(sums)
+        ptr, n = self._adafactor_ws(ws)
+        L.check(L.lib().gs_came_moment(self.handle, float(beta1), float(beta3), float(eps2), float(d),
+                                       sums.data_ptr(), ptr, n, self._stream(stream)), "gs_came_moment")
+
+    def came_step(self, beta1, beta3, eps2, d, lr, weight_decay, sums: torch.Tensor, ws: torch.Tensor, stream=None):
+        """Stage 2 of the lane regimes and p = p + p*(-wd*lr) - lr * m * (Rf * Cf) of every
+        tensor (gs_came_step); the same beta1, beta3, eps2, d as :meth:`came_moment`."""
+        self._came_sums(sums)
+        ptr, n = self._adafactor_ws(ws)
+        L.check(L.lib().gs_came_step(self.handle, float(beta1), float(beta3), float(eps2), float(d), float(lr),
+                                     float(weight_decay), sums.data_ptr(), ptr, n, self._stream(stream)),
+                "gs_came_step")
+
     # ------------------------------------------------------------------- EMA
     def ema(self, src_dtype, weight=0.0, copy=False, lowp_dtype=None, stream=None):
         """The weight average on slots 0 = average (fp32), 1 = source (``src_dtype``):

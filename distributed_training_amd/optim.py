@@ -1058,6 +1058,116 @@ class FusedAdafactor(_FusedBase):
         return loss
 
 
+class FusedCAME(_FusedBase):
+    """CAME (Luo et al., ACL 2023; ``colossalai.nn.optimizer.CAME``: signature, defaults,
+    validation and state keys, so a ``state_dict()`` moves across): Adafactor's factored second
+    moment, a full-size momentum ``exp_avg`` of the clipped direction, and a second pair of
+    factors over the instability ``(û - m)²`` that scales the momentum into the update.
+
+    The published code runs about 30 launches per parameter and step.  Here a step over a
+    param group is at most 9 grouped launches whatever the number of tensors and nothing is
+    read back: ``gs_came_stats`` (r, c and the per-tensor Σu²), ``gs_came_moment`` and
+    ``gs_came_step``.  The arithmetic is the contract in ``include/gsync.h``; every sum's order
+    is fixed by the layout, so results agree with the published code to fp32 rounding and are
+    bit-reproducible run to run.
+
+    State per parameter: ``step`` (an int), ``exp_avg``, and ``exp_avg_sq_row`` /
+    ``exp_avg_sq_col`` / ``exp_avg_res_row`` / ``exp_avg_res_col`` for ``ndim >= 2``, else
+    ``exp_avg_sq``.  The published code's informational ``RMS`` entry is not kept.
+
+    Parameters are those ``FusedAdafactor`` accepts: dense fp32 with fp32 grads in the same
+    layout, 0-D, 1-D (not factored), contiguous 2-D, and 4-D filters, contiguous or
+    ``channels_last`` (factored over ``(kh, kw)`` with ``(O, I)`` as the batch, 1x1 filters
+    included).  A parameter whose grad is None is skipped and its ``step`` does not advance.
+
+    Errors: 16-bit parameters or grads, ``grad_scale`` / ``found_inf`` (AMP), capture.  Not
+    supported: ZeRO sharding, the DeepSpeed / ColossalAI shims, ``DDP._register_fused_optim``.
+    """
+
+    _name = "FusedCAME"
+    _timer_kinds = (L.GS_OP_CAME_STATS, L.GS_OP_CAME_MOMENT, L.GS_OP_CAME_STEP)
+    _FACTORS = ("exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_res_row", "exp_avg_res_col")
+
+    def __init__(self, params, lr=None, eps=(1e-30, 1e-16), clip_threshold=1.0, betas=(0.9, 0.999, 0.9999),
+                 weight_decay=0.0):
+        if lr is None or not lr > 0.0:
+            raise ValueError(f"FusedCAME: lr is required and must be > 0 (got {lr})")
+        if len(betas) != 3 or not all(0.0 <= beta <= 1.0 for beta in betas):
+            raise ValueError(f"FusedCAME: the three betas must lie in [0, 1] (got {betas})")
+        defaults = dict(lr=lr, eps=eps, clip_threshold=clip_threshold, betas=betas, weight_decay=weight_decay)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            for p in group["params"]:
+                _adafactor_descriptor(p)
+
+    def _state(self, p):
+        """The parameter's state, created as the published code creates it; slots 2 to 6 of its plan."""
+        st = self.state[p]
+        g = p.grad
+        if len(st) == 0:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(g, memory_format=torch.preserve_format)
+            if g.dim() >= 2:
+                for key in self._FACTORS:
+                    st[key] = g.new_zeros(g.shape[:-2] + g.shape[-1:] if key.endswith("col") else g.shape[:-1])
+            else:
+                st["exp_avg_sq"] = torch.zeros_like(g)
+        if st["exp_avg"].stride() != p.stride() or st["exp_avg"].dtype != torch.float32:  # a loaded state
+            m = torch.empty_like(p, memory_format=torch.preserve_format)
+            st["exp_avg"] = m.copy_(st["exp_avg"])
+        keys = self._FACTORS if g.dim() >= 2 else ("exp_avg_sq",)
+        for key in keys:  # the kernels index the factors contiguously
+            if not (st[key].is_contiguous() and st[key].dtype == torch.float32):
+                st[key] = st[key].to(torch.float32).contiguous()
+        if g.dim() >= 2:
+            return [st[k] for k in self._FACTORS[:2]] + [st["exp_avg"]] + [st[k] for k in self._FACTORS[2:]]
+        return [st["exp_avg_sq"], None, st["exp_avg"], None, None]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self.grad_scale is not None or self.found_inf is not None:
+            raise RuntimeError("FusedCAME does not support grad_scale / found_inf (unscale the grads and skip "
+                               "the step on the host)")
+        if _capturing():
+            raise RuntimeError("FusedCAME does not support graph capture")
+        for group in self.param_groups:
+            ps, slots = [], ([], [], [], [], [], [])  # slots 1 to 6
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                self._check_param(p)
+                if p.grad.dtype != torch.float32:
+                    raise RuntimeError(f"FusedCAME expects fp32 grads (got {p.grad.dtype})")
+                state = self._state(p)
+                self.state[p]["step"] += 1
+                ps.append(p)
+                for lst, x in zip(slots, [p.grad] + state):
+                    lst.append(x)
+            if not ps:
+                continue
+            plan = self._plans.get(ps)
+            plan.set_ptrs(0, ps)
+            plan.set_ptrs(1, slots[0])
+            for slot, lst in enumerate(slots[1:], start=2):  # the factors are smaller than their tensor: raw pointers
+                plan.set_ptrs(slot, [None if x is None else x.data_ptr() for x in lst])
+            ws = getattr(plan, "_adafactor_space", None)
+            if ws is None:
+                descs, vectors = zip(*(_adafactor_descriptor(p) for p in ps))
+                plan.adafactor_layout(descs, vectors)
+                ws = plan._adafactor_space = plan.adafactor_workspace()
+                plan._norms = torch.zeros(len(ps), dtype=torch.float32, device=ps[0].device)
+            (eps1, eps2), (beta1, beta2, beta3) = group["eps"], group["betas"]
+            plan.came_stats(beta2, eps1, plan._norms, ws)
+            plan.came_moment(beta1, beta3, eps2, group["clip_threshold"], plan._norms, ws)
+            plan.came_step(beta1, beta3, eps2, group["clip_threshold"], group["lr"], group["weight_decay"],
+                           plan._norms, ws)
+        return loss
+
+
 _NORM_PLANS: dict = {}
 
 

@@ -169,7 +169,7 @@ int gs_broadcast(gs_comm* c, const void* send, void* recv, int64_t count, int dt
  * replaces: T:include/ATen/native/cuda/MultiTensorApply.cuh:14-21 launch
  *           geometry (kILP 4, 64Ki-element chunks, <=110 tensors/launch)
  * ==================================================================== */
-#define GS_PLAN_SLOTS 5
+#define GS_PLAN_SLOTS 7
 int gs_plan_create(int device_kind, int device, int n_tensors, const int64_t* numels,
                    int64_t align_elems, gs_plan** out);
 /* as gs_plan_create, with the work decomposition's task size pinned
@@ -221,6 +221,9 @@ int64_t gs_plan_task_units(gs_plan* p);
 #define GS_OP_PSGD_RECONSTRUCT 22
 #define GS_OP_ADAFACTOR_STATS 23 /* gs_adafactor_stats: one record per launch (up to 5) */
 #define GS_OP_ADAFACTOR_STEP 24  /* gs_adafactor_step: one record per launch (up to 2) */
+#define GS_OP_CAME_STATS 25  /* gs_came_stats: one record per launch (up to 5) */
+#define GS_OP_CAME_MOMENT 26 /* gs_came_moment: one record per launch (up to 2) */
+#define GS_OP_CAME_STEP 27   /* gs_came_step: one record per launch (up to 2) */
 int gs_plan_timer_enable(gs_plan* p, int n_slots);
 int gs_plan_timer_read(gs_plan* p, float* ms_out, int32_t* kind_out, int cap);
 /* register the per-tensor pointers of one slot (uploads on change, ordered on `stream`) */
@@ -688,6 +691,52 @@ int gs_adafactor_stats(gs_plan* p, double w, double eps1, float* sums_out, float
 /* sums: gs_adafactor_stats' output for this step; eps1 must be the same in both calls */
 int gs_adafactor_step(gs_plan* p, double rho, double lr, double weight_decay, double eps1, double eps2, double d,
                       int maximize, const float* sums, const float* ws, int64_t ws_elems, void* stream);
+
+/* CAME (Luo et al., ACL 2023; colossalai.nn.optimizer.CAME): Adafactor's factored second
+ * moment (r, c), a full-size momentum m of the clipped direction, and a second pair of factors
+ * (R, C) over the instability (û - m)².  û needs the tensor-wide Σu², and R, C need every û of
+ * their matrix, so a step is three calls in this order, at most 9 launches whatever the number
+ * of tensors (gs_came_stats up to 5, gs_came_moment up to 2, gs_came_step up to 2; 3 for a
+ * list without tiled tensors, 7 for one with tiled tensors only), nothing read back.
+ *
+ * Descriptors, regimes, task tables and the workspace are gs_adafactor_layout's (call it
+ * first; a 1-D or 0-D tensor is a vector there and is not factored).  Slots: 0 = p, 1 = g,
+ * 2 = r [O, I, R] or v of a vector, 3 = c [O, I, C], 4 = m (p's strides), 5 = R [O, I, R],
+ * 6 = C [O, I, C]; 3, 5, 6 unbound for a vector; 2, 3, 5, 6 contiguous; all fp32.
+ * Arithmetic (every operation rounded once, no fma; formed on the host in double and rounded
+ * to fp32: the betas, 1 - beta, eps1, eps2, d, lr, -weight_decay*lr), per matrix of the batch:
+ *   gs_came_stats:
+ *     s_ij = g_ij*g_ij + eps1
+ *     r_i  = r_i*β2 + ((Σ_j s_ij) / C)*(1-β2)       the sum, then ONE true division
+ *     c_j  = c_j*β2 + ((Σ_i s_ij) / R)*(1-β2)
+ *     u_ij = g_ij * (rf_i * cf_j),  rf_i = 1 / sqrt(r_i / ((Σ_i r_i) / R)),  cf_j = 1 / sqrt(c_j)
+ *     a vector:  v = v*β2 + s*(1-β2);  u = g * (1 / sqrt(v))
+ *     sums_out[t] = Σu² over the whole tensor
+ *   gs_came_moment / gs_came_step, from sums (u recomputed from g and the stored factors):
+ *     û    = u / max(1, sqrt(Σu² / numel) / d)      one IEEE division per element
+ *     m    = m*β1 + û*(1-β1)                         stored
+ *     q_ij = (û_ij - m_ij)*(û_ij - m_ij) + eps2
+ *     R_i  = R_i*β3 + ((Σ_j q_ij) / C)*(1-β3);  C_j = C_j*β3 + ((Σ_i q_ij) / R)*(1-β3)
+ *     upd_ij = m_ij * (Rf_i * Cf_j), Rf and Cf from R and C as rf and cf;  a vector: upd = m
+ *     p = p + p*(-weight_decay*lr)  if weight_decay != 0;   p = p - lr*upd
+ *   Which call advances what: gs_came_moment m, R, C of the tiled tensors; gs_came_step the
+ *   lane regimes' m, R, C (one launch with their update) and every p.  The host backend
+ *   advances every m, R, C in gs_came_moment.  Both calls take the same beta1, beta3, eps2, d.
+ * Orders of accumulation are gs_adafactor_stats' (above), with s or q in place of g²: a lane
+ * regime adds a row over ascending j, a column over ascending i, Σ_i r_i and Σ_i R_i over
+ * ascending i; the tiled regime adds a lane's 4 columns, the wave tree, the column blocks in
+ * order (rows), a wave's 16 rows, the 4 waves, the row blocks in order (columns), and Σ_i r_i,
+ * Σ_i R_i as rows k, k + 256, .. per thread, the wave tree, the 4 waves; Σu² partials (one per
+ * task, no Σp²) and their fold as there.  No atomics: bit-reproducible run to run; the host
+ * backend adds everything in ascending index order.
+ * GS_ESTATE: no layout, a plan clip.  GS_EINVAL: an unbound slot, a short workspace (HIP).
+ * Not part of CAME here: 16-bit tensors, grad_scale / found_inf, capture of the layout call.
+ * replaces: colossalai/nn/optimizer/came.py CAME.step (about 30 launches per parameter) */
+int gs_came_stats(gs_plan* p, double beta2, double eps1, float* sums_out, float* ws, int64_t ws_elems, void* stream);
+int gs_came_moment(gs_plan* p, double beta1, double beta3, double eps2, double d, const float* sums, float* ws,
+                   int64_t ws_elems, void* stream);
+int gs_came_step(gs_plan* p, double beta1, double beta3, double eps2, double d, double lr, double weight_decay,
+                 const float* sums, const float* ws, int64_t ws_elems, void* stream);
 
 /* EMA / SWA weight averaging: one pass a' = lerp(a, s, w) over a whole model.
  * Slots: 0 = the average a (f32), 1 = the source s (src_dtype: f32, bf16 or f16, converted
